@@ -29,14 +29,22 @@ reference-exact 1 MiB contract (294,912 device IDs per 288 GB GPU).
 Configs (--config): mixed (default; core fractions + memory fractions, 16
 pods/GPU oversubscribed), whole-gpu, mem-fraction, compute-fraction,
 kind-fake (forces the fake backend).
+
+A plain run does only what the headline needs: set up, warm up, time
+--steps steps, print the line. `--dump-outputs DIR` additionally saves what
+the last timed step produced (see dump_outputs). `--full` is where any
+measurement beyond the headline belongs (baselines, other scenarios,
+per-stage attribution); the benchmark has none today — other scenarios and
+agent shapes are separate invocations via --config / --agent-mode /
+--workers — so the flag is accepted and changes nothing.
 """
 from __future__ import annotations
 
 import argparse
 import json
 import os
+import shutil
 import sys
-import tempfile
 import time
 
 REPO = os.path.dirname(os.path.abspath(__file__))
@@ -112,6 +120,63 @@ def install_backend(h, backend):
         h.storage, backend.devices(),
         on_remask=lambda hh, m, n: h.plugin.cfg.limits.update_in_place(
             hh, cu_mask=m, cu_count=n))
+
+
+def response_rows(responses, root):
+    """One row per pod from its decoded AllocateResponse: device-set hash,
+    env / device / mount counts, and a CRC32 of the whole response with the
+    per-run scratch root masked out (equal responses give equal rows)."""
+    import zlib
+
+    from elastic_gpu_agent_amd import consts
+
+    rows = []
+    for resp in responses:
+        cr = resp["container_responses"][0]
+        canon = json.dumps(resp, sort_keys=True).replace(root, "<root>")
+        rows.append([int(cr["envs"][consts.GPU_ENV_KEY], 16),
+                     len(cr.get("envs", {})), len(cr.get("devices", [])),
+                     len(cr.get("mounts", [])), zlib.crc32(canon.encode())])
+    return rows
+
+
+def binding_rows(limits, hashes):
+    """One row per bound pod from the limits file PreStart wrote for it:
+    device-set hash, GPU index, number of render nodes bound (the minor
+    itself names the card, not the computation), CU count and HBM quota (0 =
+    unlimited), then the CU mask as 32-bit words."""
+    from elastic_gpu_agent_amd.isolation.cumask import parse_mask_hex
+
+    recs = [limits.read(h) for h in hashes]
+    masks = [parse_mask_hex(r.get("cu_mask", "")) for r in recs]
+    width = max((len(m) for m in masks), default=0)
+    rows = []
+    for h, r, m in zip(hashes, recs, masks):
+        rows.append([int(h, 16), r["gpu_indexes"][0],
+                     len(r.get("render_minors", [])),
+                     r.get("cu_count", 0), r.get("mem_limit_bytes", 0)]
+                    + m + [0] * (width - len(m)))
+    return rows
+
+
+def dump_outputs(out_dir, responses, bindings):
+    """--dump-outputs: what a caller of the timed path holds after the LAST
+    timed step, as float64 arrays (every value is an integer < 2**53, so
+    exact). Inputs are fixed by the arguments, so two builds run with the
+    same arguments can be compared array for array.
+
+      allocate_responses.npy  [pods, 5]     response_rows() of rank 0's pods
+      bindings.npy            [pods, 5+W]   binding_rows() of every rank's
+                                            pods, read after PreStart and
+                                            before the step's teardown
+    """
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "allocate_responses.npy"),
+            np.asarray(responses, dtype=np.float64))
+    np.save(os.path.join(out_dir, "bindings.npy"),
+            np.asarray(bindings, dtype=np.float64))
 
 
 def emit(rank, value, elapsed_max, args, world, n_gpus, pods_per_step_job,
@@ -209,7 +274,7 @@ def run_single_agent(args, rank, world, dist):
 
     from elastic_gpu_agent_amd import consts
     from elastic_gpu_agent_amd.types import Device, PodContainer
-    from helpers import Harness, PluginClient
+    from helpers import Harness, PluginClient, short_tmpdir
 
     backend, backend_name = (None, "fake-gfx950")
     h = None
@@ -217,7 +282,7 @@ def run_single_agent(args, rank, world, dist):
     listen_socks = []
     if rank == 0:
         backend, backend_name = pick_backend(args.config)
-        tmp = tempfile.mkdtemp(prefix="egpu-bench-agent-")
+        tmp = short_tmpdir("egpu-bench-agent-")
         # fake-backend GPU count (EGPU_BENCH_GPUS lets tests model fewer
         # GPUs than ranks — the shape a 1-GPU box gives a multi-rank run)
         n_fake = int(os.environ.get("EGPU_BENCH_GPUS", world))
@@ -303,6 +368,10 @@ def run_single_agent(args, rank, world, dist):
     ]
 
     alloc_lat, prestart_lat = [], []
+    # --dump-outputs: each pod's latest AllocateResponse (overwritten every
+    # step) and, from the last timed step, the bindings PreStart left
+    last_responses = [None] * len(encoded_plans)
+    last_bindings = []
 
     # Precompute every (rank, pod) device hash once: the ID sets repeat
     # every step (only the pod name changes), and the kubelet stand-in must
@@ -334,7 +403,7 @@ def run_single_agent(args, rank, world, dist):
         for p, (kind, alloc_raw, pre_raw) in enumerate(encoded_plans):
             client = core if kind == "core" else mem
             t0 = time.perf_counter()
-            client.allocate_raw(alloc_raw)
+            last_responses[p] = client.allocate_raw(alloc_raw)
             t1 = time.perf_counter()
             client.pre_start_raw(pre_raw)
             t2 = time.perf_counter()
@@ -362,6 +431,9 @@ def run_single_agent(args, rank, world, dist):
         drive_step(step_i)
         barrier()
         if rank == 0:
+            if args.dump_outputs and step_i == args.steps - 1:
+                last_bindings.extend(binding_rows(
+                    h.plugin.cfg.limits, [pl[3] for pl in all_plans]))
             teardown_step(step_i)
 
     for w in range(args.warmup):
@@ -381,6 +453,10 @@ def run_single_agent(args, rank, world, dist):
     pods_job = world * pods_per_step
     value = pods_job * args.steps / elapsed_max
 
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, response_rows(last_responses, tmp),
+                     last_bindings)
+
     core.close()
     mem.close()
     for p in worker_procs:
@@ -394,7 +470,8 @@ def run_single_agent(args, rank, world, dist):
         s.close()
     if h is not None:
         h.close()
-    mode = (f"1 agent x {world} GPUs ({world} load ranks, "
+        shutil.rmtree(tmp, ignore_errors=True)
+    mode =(f"1 agent x {world} GPUs ({world} load ranks, "
             f"{args.workers} workers)" if args.workers > 0
             else f"1 agent x {world} GPUs ({world} load ranks)")
     emit(rank, value, elapsed_max, args, world, len(gpu_list), pods_job,
@@ -407,10 +484,10 @@ def run_per_gpu(args, rank, world, dist):
 
     from elastic_gpu_agent_amd import consts
     from elastic_gpu_agent_amd.types import Device, PodContainer
-    from helpers import Harness, PluginClient
+    from helpers import Harness, PluginClient, short_tmpdir
 
     backend, backend_name = pick_backend(args.config)
-    tmp = tempfile.mkdtemp(prefix=f"egpu-bench-r{rank}-")
+    tmp = short_tmpdir(f"egpu-bench-r{rank}-")
     h = Harness(tmp, gpus=1, mem_unit_mib=args.mem_unit_mib)
     install_backend(h, backend)
     gpus = h.plugin.cfg.operator.devices()
@@ -427,6 +504,8 @@ def run_per_gpu(args, rank, world, dist):
                      args.mem_unit_mib)
     pods_per_step = len(plans)
     alloc_lat, prestart_lat = [], []
+    last_responses = [None] * len(plans)  # --dump-outputs, as in single mode
+    last_bindings = []
 
     def one_step(step_i: int):
         pods = []
@@ -439,13 +518,17 @@ def run_per_gpu(args, rank, world, dist):
             h.add_assumed_pod(ns, name, container, str(gpu.index))
             client = core if kind == "core" else mem
             t0 = time.perf_counter()
-            client.allocate({"container_requests": [{"devicesIDs": ids}]})
+            last_responses[p] = client.allocate(
+                {"container_requests": [{"devicesIDs": ids}]})
             t1 = time.perf_counter()
             client.pre_start({"devicesIDs": ids})
             t2 = time.perf_counter()
             alloc_lat.append(t1 - t0)
             prestart_lat.append(t2 - t1)
             pods.append((ns, name, d))
+        if rank == 0 and args.dump_outputs and step_i == args.steps - 1:
+            last_bindings.extend(binding_rows(
+                h.plugin.cfg.limits, [d.hash for _, _, d in pods]))
         for ns, name, _ in pods:
             h.sitter.remove(ns, name)
         reclaimed = h.plugin.gc_once()
@@ -471,9 +554,13 @@ def run_per_gpu(args, rank, world, dist):
     elapsed_max, p50_us, p99_us, p50_pre = reduce_stats(
         dist, torch, elapsed, alloc_lat, prestart_lat)
     value = world * pods_per_step * args.steps / elapsed_max
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, response_rows(last_responses, tmp),
+                     last_bindings)
     core.close()
     mem.close()
     h.close()
+    shutil.rmtree(tmp, ignore_errors=True)
     emit(rank, value, elapsed_max, args, world, world, world * pods_per_step,
          p50_us, p99_us, p50_pre, backend_name,
          f"dp{world} (1 agent per GPU)")
@@ -501,6 +588,12 @@ def main():
                          "handler concurrency for cross-process state "
                          "coordination — wins when handlers dominate, loses "
                          "when the shared single-file store does)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, save what the last one "
+                         "produced as DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run measurements beyond the headline figure "
+                         "(none exist today; a plain run is already complete)")
     args = ap.parse_args()
 
     rank, world = get_dist()

@@ -394,17 +394,26 @@ class DbCUMaskAllocator:
 
         self._devices = list(devices)
         self.on_remask = on_remask
-        self._conn = sqlite3.connect(db_path, check_same_thread=False)
-        self._conn.execute("PRAGMA journal_mode=WAL")
-        self._conn.execute("PRAGMA busy_timeout=10000")
-        self._conn.execute(
-            "CREATE TABLE IF NOT EXISTS aux (key TEXT PRIMARY KEY, val TEXT NOT NULL)"
-        )
-        self._conn.commit()
-        self._local = threading.Lock()
+        import fcntl
+
         # same flock sidecar as Storage: cross-process handoff at kernel
         # granularity instead of sqlite's sleepy busy handler
         self._flock_fd = os.open(db_path + ".lock", os.O_CREAT | os.O_RDWR, 0o644)
+        self._conn = sqlite3.connect(db_path, check_same_thread=False)
+        # held across setup too: workers opening a fresh file together would
+        # otherwise fail the WAL switch with "database is locked" (it needs
+        # the database to itself and does not wait)
+        fcntl.flock(self._flock_fd, fcntl.LOCK_EX)
+        try:
+            self._conn.execute("PRAGMA journal_mode=WAL")
+            self._conn.execute("PRAGMA busy_timeout=10000")
+            self._conn.execute(
+                "CREATE TABLE IF NOT EXISTS aux (key TEXT PRIMARY KEY, val TEXT NOT NULL)"
+            )
+            self._conn.commit()
+        finally:
+            fcntl.flock(self._flock_fd, fcntl.LOCK_UN)
+        self._local = threading.Lock()
         # version-cached occupancy: every mutating txn (any process) bumps
         # maskver under the flock, so the full aux rescan happens only when
         # ANOTHER process changed the mask set since our last txn

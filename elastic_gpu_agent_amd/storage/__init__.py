@@ -50,6 +50,17 @@ class Storage:
         # kernel-granularity handoff instead (uncontended cost ~2 µs).
         self._flock_fd = os.open(db_path + ".lock", os.O_CREAT | os.O_RDWR, 0o644)
         self._conn = sqlite3.connect(db_path, check_same_thread=False)
+        # Pre-forked workers open the same fresh file at the same moment, and
+        # the switch to WAL needs the database to itself (sqlite fails it with
+        # "database is locked" at once, busy handler or not): set up one
+        # process at a time.
+        fcntl.flock(self._flock_fd, fcntl.LOCK_EX)
+        try:
+            self._init_db()
+        finally:
+            fcntl.flock(self._flock_fd, fcntl.LOCK_UN)
+
+    def _init_db(self) -> None:
         # 32 KB pages: ~30% faster 700 KB-record saves than the 4 KB default
         # (fewer page headers/copies); applies to newly created DB files only
         self._conn.execute("PRAGMA page_size=32768")

@@ -22,6 +22,34 @@ from elastic_gpu_agent_amd.protos import deviceplugin as dp
 from elastic_gpu_agent_amd.storage import Storage
 
 
+# sockaddr_un.sun_path holds 107 bytes + NUL. The longest path the harness
+# hangs off its root is device-plugins/elastic-gpushare-memory.sock (43) and
+# tests add a sub-directory level of their own; roots up to this length
+# always fit.
+SOCKET_ROOT_MAX = 56
+
+
+def short_tmp_base(prefix: str = "egpu-") -> str:
+    """The temp directory in which mkdtemp(prefix=prefix) leaves room for the
+    agent's unix sockets: $TMPDIR unless it is too deeply nested, then a
+    short world-writable one."""
+    import tempfile
+
+    base = tempfile.gettempdir()
+    if len(base) + 1 + len(prefix) + 8 > SOCKET_ROOT_MAX:
+        for cand in ("/tmp", "/var/tmp", "/dev/shm"):
+            if os.path.isdir(cand) and os.access(cand, os.W_OK | os.X_OK):
+                return cand
+    return base
+
+
+def short_tmpdir(prefix: str = "egpu-") -> str:
+    """mkdtemp() under short_tmp_base(). The caller removes the directory."""
+    import tempfile
+
+    return tempfile.mkdtemp(prefix=prefix, dir=short_tmp_base(prefix))
+
+
 @dataclass
 class Harness:
     tmp: str

@@ -129,13 +129,10 @@ def test_listandwatch_wire_delivery_8gpu_1mib(tmp_path):
     re-reads it on every reconnect): raw-stream the 58 MB mem snapshot and
     bound the time. (Decode here is the Go kubelet's job; our Python
     decode of 2.36 M devices takes ~26 s and is not on any agent path.)"""
-    import tempfile
-
     from elastic_gpu_agent_amd import egrpc
     from elastic_gpu_agent_amd.protos import deviceplugin as dp
 
-    tmp = tempfile.mkdtemp()
-    h = Harness(tmp, gpus=8, mem_unit_mib=1)
+    h = Harness(str(tmp_path), gpus=8, mem_unit_mib=1)
     h.plugin.memory_server.serve()
     h.plugin.memory_server.wait_ready()
     ch = egrpc.Channel(h.plugin.memory_server.socket_path)

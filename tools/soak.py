@@ -12,8 +12,8 @@ from __future__ import annotations
 
 import argparse
 import os
+import shutil
 import sys
-import tempfile
 import threading
 import time
 
@@ -41,12 +41,12 @@ def main():
                     help="additional allowance per bind cycle")
     args = ap.parse_args()
 
-    from helpers import Harness, PluginClient
+    from helpers import Harness, PluginClient, short_tmpdir
 
     from elastic_gpu_agent_amd import consts
     from elastic_gpu_agent_amd.types import Device, PodContainer
 
-    tmp = tempfile.mkdtemp(prefix="egpu-soak-")
+    tmp = short_tmpdir("egpu-soak-")
     h = Harness(tmp, gpus=2)
     try:
         import torch
@@ -173,6 +173,7 @@ def main():
     _malloc_trim()
     rss1 = rss_mb()
     h.close()
+    shutil.rmtree(tmp, ignore_errors=True)
     growth = rss1 - rss0
     allowed = args.rss_limit_mb + counts["prestart"] * args.rss_per_cycle_bytes / 1e6
     print(f"soak: {counts} rss {rss0:.1f} -> {rss1:.1f} MB "

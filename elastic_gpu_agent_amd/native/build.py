@@ -58,7 +58,7 @@ def build_fastwire(force=False):
     src = os.path.join(HERE, "fastwire.cpp")
     ext = sysconfig.get_config_var("EXT_SUFFIX")
     out = os.path.join(PKG, f"_fastwire{ext}")
-    if not force and _newer(out, src):
+    if not force and _newer(out, src, os.path.join(HERE, "wirecore.h")):
         return out
     _run(
         ["g++", "-O2", "-std=c++17", "-shared", "-fPIC", src]
@@ -76,7 +76,7 @@ def build_etransport(force=False):
         _run([sys.executable, gen])
     ext = sysconfig.get_config_var("EXT_SUFFIX")
     out = os.path.join(PKG, f"_etransport{ext}")
-    if not force and _newer(out, src, tables):
+    if not force and _newer(out, src, tables, os.path.join(HERE, "h2core.h")):
         return out
     _run(
         ["g++", "-O2", "-g", "-std=c++17", "-shared", "-fPIC", src]

@@ -1,8 +1,11 @@
-"""Build + (optionally) run the libFuzzer harness over the native parsers.
+"""Build + (optionally) run the libFuzzer harness over the native parsers,
+and the stand-alone sanitizer self-test of the device-set digest.
 
 Usage:
   python -m elastic_gpu_agent_amd.native.build_fuzz             # build only
   python -m elastic_gpu_agent_amd.native.build_fuzz --run 60    # fuzz 60 s
+  python -m elastic_gpu_agent_amd.native.build_fuzz --replay    # in-tree corpus, once
+  python -m elastic_gpu_agent_amd.native.build_fuzz --selftest  # ASan+UBSan digest cases
 """
 from __future__ import annotations
 
@@ -40,8 +43,37 @@ def run(binary, seconds=30, corpus=None):
     return subprocess.call(cmd)
 
 
+def replay(binary, corpus=None):
+    """Run every input of the checked-in corpus through the harness once."""
+    corpus = corpus or os.path.join(REPO, "tests", "fuzz_regressions_corpus")
+    inputs = sorted(os.path.join(corpus, f) for f in os.listdir(corpus))
+    cmd = [binary, *inputs]
+    print("+", binary, f"<{len(inputs)} corpus inputs>", flush=True)
+    return subprocess.call(cmd)
+
+
+def build_selftest(out=None):
+    """digest_selftest.cpp: wirecore.h's fused digest against a naive
+    reference, as an ordinary program with ASan + UBSan (no fuzzer runtime)."""
+    out = out or os.path.join(REPO, "bin", "egpu-digest-selftest")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    cmd = [
+        CLANGXX, "-O1", "-g", "-std=c++17",
+        "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+        os.path.join(HERE, "digest_selftest.cpp"),
+        "-I", HERE, "-o", out,
+    ]
+    print("+", " ".join(cmd), flush=True)
+    subprocess.check_call(cmd)
+    return out
+
+
 if __name__ == "__main__":
+    if "--selftest" in sys.argv:
+        sys.exit(subprocess.call([build_selftest()]))
     binary = build()
+    if "--replay" in sys.argv:
+        sys.exit(replay(binary))
     if "--run" in sys.argv:
         secs = int(sys.argv[sys.argv.index("--run") + 1])
         sys.exit(run(binary, secs))

@@ -28,6 +28,7 @@
 #include <csignal>
 #include <execinfo.h>
 #include <sys/socket.h>
+#include <sys/uio.h>
 #include <sys/un.h>
 #include <thread>
 #include <unistd.h>
@@ -134,13 +135,162 @@ std::string error_trailer_block(int code, const std::string& message) {
   return out;
 }
 
-ssize_t read_some(int fd, uint8_t* buf, size_t n) { return ::read(fd, buf, n); }
+// ---------------------------------------------------------------- buffers
+// Receive buffer shared by the server connection and the client: read()
+// lands directly in its tail and frames are handed out as views into it, so
+// a warm connection neither allocates nor copies per request. Capacity is
+// kept across requests; above kRetainCap (one huge ListAndWatch snapshot or
+// GetPreferredAllocation pool) it is given back once the traffic is small
+// again.
+//
+// A view handed out by head() dies at the next read_more(): that call may
+// overwrite, move or reallocate the storage.
+class RecvBuf {
+ public:
+  static constexpr size_t kInitCap = 256 * 1024;
+  static constexpr size_t kMinRead = 64 * 1024;
+  static constexpr size_t kRetainCap = 4u << 20;
+
+  RecvBuf() = default;
+  RecvBuf(const RecvBuf&) = delete;
+  RecvBuf& operator=(const RecvBuf&) = delete;
+  ~RecvBuf() { free(data_); }
+
+  size_t avail() const { return end_ - pos_; }
+  const uint8_t* head() const { return data_ + pos_; }
+  void consume(size_t n) { pos_ += n; }
+  void clear() { pos_ = end_ = 0; }
+
+  // one read() into the tail, after making room for `need` contiguous
+  // bytes from head(); returns what read() returned
+  ssize_t read_more(int fd, size_t need) {
+    size_t live = end_ - pos_;
+    if (live == 0) pos_ = end_ = 0;
+    size_t room = std::max(need > live ? need - live : (size_t)0, kMinRead);
+    size_t req = live + room;
+    if (cap_ > kRetainCap && req <= kRetainCap / 2) {
+      reallocate(std::max(req, kInitCap));
+    } else if (cap_ - end_ < room) {
+      // compact only when the consumed prefix dominates; otherwise grow
+      if (pos_ > 0 && pos_ >= live) {
+        memmove(data_, data_ + pos_, live);
+        pos_ = 0;
+        end_ = live;
+      }
+      if (cap_ - end_ < room)
+        reallocate(std::max({live + room, cap_ * 2, kInitCap}));
+    }
+    ssize_t r = ::read(fd, data_ + end_, cap_ - end_);
+    if (r > 0) end_ += (size_t)r;
+    return r;
+  }
+
+ private:
+  // new storage holding only the live bytes, at the front
+  void reallocate(size_t ncap) {
+    size_t live = end_ - pos_;
+    uint8_t* n = (uint8_t*)malloc(ncap);
+    if (!n) throw std::bad_alloc();
+    if (live) memcpy(n, data_ + pos_, live);
+    free(data_);
+    data_ = n;
+    cap_ = ncap;
+    pos_ = 0;
+    end_ = live;
+  }
+
+  uint8_t* data_ = nullptr;
+  size_t cap_ = 0, pos_ = 0, end_ = 0;
+};
+
+// one received frame; `body` points into a RecvBuf (see the lifetime note)
+struct Frame {
+  uint8_t type = 0, flags = 0;
+  uint32_t sid = 0;
+  const uint8_t* body = nullptr;
+  size_t len = 0;
+};
+
+// parse the frame at the buffer head once `fill` has made it contiguous;
+// fill(n) returns false (server) or throws (client) on I/O failure
+template <class Fill>
+bool next_frame(RecvBuf& buf, Fill&& fill, Frame* f, bool* oversize) {
+  *oversize = false;
+  if (!fill(9)) return false;
+  const uint8_t* h = buf.head();
+  uint32_t len = h[0] << 16 | h[1] << 8 | h[2];
+  f->type = h[3];
+  f->flags = h[4];
+  uint32_t s;
+  memcpy(&s, h + 5, 4);
+  f->sid = ntohl(s) & 0x7fffffff;
+  if (len > 64u * 1024 * 1024) { *oversize = true; return false; }  // refuse absurd frames
+  if (!fill(9 + (size_t)len)) return false;
+  f->body = buf.head() + 9;  // re-read: the second fill may have moved it
+  f->len = len;
+  buf.consume(9 + (size_t)len);
+  return true;
+}
+
+// writev() until every byte is out; the iovec array is consumed
+bool writev_all(int fd, struct iovec* iov, int cnt) {
+  while (cnt > 0) {
+    ssize_t w = ::writev(fd, iov, cnt);
+    if (w <= 0) {
+      if (w < 0 && errno == EINTR) continue;
+      return false;
+    }
+    size_t left = (size_t)w;
+    while (cnt > 0 && left >= iov->iov_len) {
+      left -= iov->iov_len;
+      ++iov;
+      --cnt;
+    }
+    if (cnt > 0 && left) {
+      iov->iov_base = (uint8_t*)iov->iov_base + left;
+      iov->iov_len -= left;
+    }
+  }
+  return true;
+}
+
+// iovecs for bytes [off, off+n) of the logical payload prefix5 ++ msg
+int payload_iov(struct iovec* iov, const uint8_t* prefix5, const uint8_t* msg,
+                size_t off, size_t n) {
+  int k = 0;
+  if (off < 5 && n) {
+    size_t m = std::min(n, 5 - off);
+    iov[k].iov_base = (void*)(prefix5 + off);
+    iov[k].iov_len = m;
+    ++k;
+    off += m;
+    n -= m;
+  }
+  if (n) {
+    iov[k].iov_base = (void*)(msg + (off - 5));
+    iov[k].iov_len = n;
+    ++k;
+  }
+  return k;
+}
+
+void put_grpc_prefix(uint8_t* p, size_t msg_len) {
+  p[0] = 0;
+  uint32_t len = htonl((uint32_t)msg_len);
+  memcpy(p + 1, &len, 4);
+}
+
+// keep a reused string's capacity bounded (same policy as RecvBuf)
+void cap_retained(std::string& s) {
+  if (s.capacity() > RecvBuf::kRetainCap) std::string().swap(s);
+}
 
 // ---------------------------------------------------------------- streams
 struct StreamState {
   uint32_t id = 0;
   std::string path;
-  std::string data;
+  std::string data;  // request body; unused when one DATA frame carries it all
+  bool data_reserved = false;
   std::string header_accum;
   bool end_stream = false;
   bool end_headers = true;
@@ -216,9 +366,9 @@ class Connection : public std::enable_shared_from_this<Connection> {
       send_raw(out, p - out);
     }
     while (!closed_.load()) {
-      uint8_t type, flags; uint32_t sid; std::string body;
-      if (!read_frame(&type, &flags, &sid, &body)) break;
-      process_frame(type, flags, sid, body, /*defer=*/false);
+      Frame f;
+      if (!read_frame(&f)) break;
+      process_frame(f, /*defer=*/false);
       while (!deferred_.empty()) {
         uint32_t id = deferred_.front();
         deferred_.pop_front();
@@ -228,7 +378,7 @@ class Connection : public std::enable_shared_from_this<Connection> {
           auto it = streams_.find(id);
           if (it != streams_.end()) stp = &it->second;
         }
-        if (stp) dispatch(*stp);
+        if (stp) dispatch(*stp, (const uint8_t*)stp->data.data(), stp->data.size());
       }
       // bound per-connection recv-deficit bookkeeping: entries accumulate one
       // per stream id; safe to drop whenever no stream is open (conn thread
@@ -250,56 +400,45 @@ class Connection : public std::enable_shared_from_this<Connection> {
  private:
   // ---- io ----
   bool fill(size_t need) {
-    while (buf_.size() - pos_ < need) {
-      uint8_t tmp[262144];
-      ssize_t r = read_some(fd_, tmp, sizeof(tmp));
+    while (buf_.avail() < need) {
+      ssize_t r = buf_.read_more(fd_, need);
+      if (r < 0 && errno == EINTR) continue;
       if (r <= 0) return false;
-      buf_.append((const char*)tmp, r);
-      if (pos_ > (1 << 20) && pos_ * 2 > buf_.size()) {
-        buf_.erase(0, pos_);
-        pos_ = 0;
-      }
     }
     return true;
   }
 
-  bool read_frame(uint8_t* type, uint8_t* flags, uint32_t* sid, std::string* body) {
-    if (!fill(9)) return false;
-    const uint8_t* h = (const uint8_t*)buf_.data() + pos_;
-    uint32_t len = h[0] << 16 | h[1] << 8 | h[2];
-    *type = h[3];
-    *flags = h[4];
-    uint32_t s;
-    memcpy(&s, h + 5, 4);
-    *sid = ntohl(s) & 0x7fffffff;
-    if (len > 64u * 1024 * 1024) return false;  // refuse absurd frames
-    if (!fill(9 + len)) return false;
-    body->assign(buf_.data() + pos_ + 9, len);
-    pos_ += 9 + len;
-    return true;
+  // f->body is a view into buf_: it dies at the next read_frame(), and
+  // anything that can pump (send_message(pump=true), hence dispatch of a
+  // unary call) reads frames. Finish with the view, or copy, before that.
+  bool read_frame(Frame* f) {
+    bool oversize;
+    return next_frame(buf_, [this](size_t n) { return fill(n); }, f, &oversize);
   }
 
   void send_raw(const void* data, size_t n) {
+    struct iovec iov{(void*)data, n};
+    send_iov(&iov, 1);
+  }
+
+  void send_iov(struct iovec* iov, int cnt) {
     std::lock_guard<std::mutex> lk(write_mu_);
-    const uint8_t* p = (const uint8_t*)data;
-    size_t off = 0;
-    while (off < n) {
-      ssize_t w = ::write(fd_, p + off, n - off);
-      if (w <= 0) { closed_.store(true); return; }
-      off += w;
-    }
+    if (!writev_all(fd_, iov, cnt)) closed_.store(true);
   }
 
   // ---- frame processing (mirrors egrpc/server.py) ----
-  void process_frame(uint8_t type, uint8_t flags, uint32_t sid,
-                     const std::string& body, bool defer) {
+  void process_frame(const Frame& f, bool defer) {
+    const uint8_t type = f.type, flags = f.flags;
+    const uint32_t sid = f.sid;
+    const uint8_t* body = f.body;
+    const size_t blen = f.len;
     switch (type) {
       case F_SETTINGS:
         if (!(flags & FLAG_ACK)) {
-          for (size_t off = 0; off + 6 <= body.size(); off += 6) {
-            uint16_t k = (uint8_t)body[off] << 8 | (uint8_t)body[off + 1];
+          for (size_t off = 0; off + 6 <= blen; off += 6) {
+            uint16_t k = body[off] << 8 | body[off + 1];
             uint32_t v;
-            memcpy(&v, body.data() + off + 2, 4);
+            memcpy(&v, body + off + 2, 4);
             v = ntohl(v);
             if (k == S_MAX_FRAME) peer_max_frame_ = v;
             else if (k == S_INITIAL_WINDOW) {
@@ -316,17 +455,17 @@ class Connection : public std::enable_shared_from_this<Connection> {
         }
         break;
       case F_PING:
-        if (!(flags & FLAG_ACK) && body.size() == 8) {
+        if (!(flags & FLAG_ACK) && blen == 8) {
           uint8_t p[17];
           put_frame_header(p, 8, F_PING, FLAG_ACK, 0);
-          memcpy(p + 9, body.data(), 8);
+          memcpy(p + 9, body, 8);
           send_raw(p, 17);
         }
         break;
       case F_WINUP: {
-        if (body.size() != 4) break;
+        if (blen != 4) break;
         uint32_t inc;
-        memcpy(&inc, body.data(), 4);
+        memcpy(&inc, body, 4);
         inc = ntohl(inc) & 0x7fffffff;
         std::lock_guard<std::mutex> lk(win_mu_);
         if (sid == 0) conn_send_window_ += inc;
@@ -343,17 +482,20 @@ class Connection : public std::enable_shared_from_this<Connection> {
         auto& st = *stp;
         st.id = sid;
         size_t off = 0, pad = 0;
-        if (flags & FLAG_PADDED) { pad = (uint8_t)body[0]; off = 1; }
+        // an empty padded frame has no pad-length byte to read
+        if (flags & FLAG_PADDED) { pad = blen ? body[0] : 0; off = 1; }
         if (flags & FLAG_PRIORITY) off += 5;
-        if (off > body.size() || pad > body.size() - off) { streams_.erase(sid); break; }
-        std::string block = body.substr(off, body.size() - off - pad);
+        if (off > blen || pad > blen - off) { streams_.erase(sid); break; }
+        const uint8_t* block = body + off;
+        size_t block_len = blen - off - pad;
         st.end_stream = st.end_stream || (flags & FLAG_END_STREAM);
         if (flags & FLAG_END_HEADERS) {
-          decode_headers(st, block);
+          // the view is done with once decoded; dispatch may pump
+          decode_headers(st, block, block_len);
           if (st.end_stream) queue_dispatch(sid, defer);
         } else {
           st.end_headers = false;
-          st.header_accum = std::move(block);
+          st.header_accum.assign((const char*)block, block_len);
           cont_sid_ = sid;
         }
         break;
@@ -364,10 +506,11 @@ class Connection : public std::enable_shared_from_this<Connection> {
         if (it == streams_.end()) break;
         auto& st = it->second;
         lk.unlock();
-        st.header_accum += body;
+        st.header_accum.append((const char*)body, blen);
         if (flags & FLAG_END_HEADERS) {
           st.end_headers = true;
-          decode_headers(st, st.header_accum);
+          decode_headers(st, (const uint8_t*)st.header_accum.data(),
+                         st.header_accum.size());
           st.header_accum.clear();
           cont_sid_ = 0;
           if (st.end_stream) queue_dispatch(st.id, defer);
@@ -381,11 +524,30 @@ class Connection : public std::enable_shared_from_this<Connection> {
         auto& st = it->second;
         lk.unlock();
         size_t off = 0, pad = 0;
-        if (flags & FLAG_PADDED) { pad = (uint8_t)body[0]; off = 1; }
-        if (off > body.size() || pad > body.size() - off) break;
-        st.data.append(body.data() + off, body.size() - off - pad);
-        if (!body.empty()) replenish(sid, body.size(), flags & FLAG_END_STREAM);
-        if (flags & FLAG_END_STREAM) {
+        if (flags & FLAG_PADDED) { pad = blen ? body[0] : 0; off = 1; }
+        if (off > blen || pad > blen - off) break;
+        const uint8_t* chunk = body + off;
+        size_t chunk_len = blen - off - pad;
+        if (blen) replenish(sid, blen, flags & FLAG_END_STREAM);
+        bool end = flags & FLAG_END_STREAM;
+        if (end && !defer && st.data.empty()) {
+          // whole body in one frame: dispatch straight from the view. The
+          // handler's bytes object is built before anything can pump.
+          st.end_stream = true;
+          dispatch(st, chunk, chunk_len);
+          break;  // `chunk` and `st` are dead here
+        }
+        st.data.append((const char*)chunk, chunk_len);
+        if (!st.data_reserved && st.data.size() >= 5) {
+          // size the body once from the gRPC length prefix, bounded by what
+          // flow control lets the peer have in flight
+          st.data_reserved = true;
+          uint32_t mlen;
+          memcpy(&mlen, st.data.data() + 1, 4);
+          size_t want = 5 + (size_t)ntohl(mlen);
+          if (!end) st.data.reserve(std::min(want, (size_t)RECV_WINDOW));
+        }
+        if (end) {
           st.end_stream = true;
           queue_dispatch(sid, defer);
         }
@@ -413,9 +575,9 @@ class Connection : public std::enable_shared_from_this<Connection> {
     }
   }
 
-  void decode_headers(StreamState& st, const std::string& block) {
+  void decode_headers(StreamState& st, const uint8_t* block, size_t n) {
     std::vector<std::pair<std::string, std::string>> hdrs;
-    if (!decoder_.decode((const uint8_t*)block.data(), block.size(), &hdrs)) {
+    if (!decoder_.decode(block, n, &hdrs)) {
       closed_.store(true);  // HPACK state is unrecoverable per-connection
       return;
     }
@@ -453,53 +615,57 @@ class Connection : public std::enable_shared_from_this<Connection> {
   }
 
   // ---- sending with flow control ----
-  // pump=true may only be used from the connection thread
-  bool send_data(uint32_t sid, const std::string& payload, bool end_stream, bool pump) {
-    size_t off = 0, total = payload.size();
-    while (off < total || (total == 0 && end_stream)) {
+  // One gRPC message (5-byte prefix + msg) as DATA frames, straight from the
+  // caller's memory: per frame one writev of frame header, prefix part and
+  // message part. pump=true may only be used from the connection thread; it
+  // reads frames while the window is closed, so every earlier frame view is
+  // dead once this returns.
+  bool send_message(uint32_t sid, const uint8_t* msg, size_t msg_len, bool pump) {
+    uint8_t prefix[5];
+    put_grpc_prefix(prefix, msg_len);
+    size_t off = 0, total = 5 + msg_len;
+    while (off < total) {
       int64_t avail;
       {
         std::lock_guard<std::mutex> lk(win_mu_);
         avail = std::min(conn_send_window_, stream_window_ref(sid));
       }
       if ((int64_t)peer_max_frame_ < avail) avail = peer_max_frame_;
-      if (total > 0 && avail <= 0) {
+      if (avail <= 0) {
         if (closed_.load()) return false;
         if (pump) {
-          uint8_t type, flags; uint32_t fsid; std::string body;
-          if (!read_frame(&type, &flags, &fsid, &body)) { closed_.store(true); return false; }
-          process_frame(type, flags, fsid, body, /*defer=*/true);
+          Frame f;
+          if (!read_frame(&f)) { closed_.store(true); return false; }
+          process_frame(f, /*defer=*/true);
         } else {
           std::unique_lock<std::mutex> lk(win_mu_);
           win_cv_.wait_for(lk, std::chrono::milliseconds(100));
         }
         continue;
       }
-      size_t n = total ? std::min((size_t)avail, total - off) : 0;
-      bool last = off + n >= total;
-      uint8_t flags = (end_stream && last) ? FLAG_END_STREAM : 0;
-      std::string frame;
-      frame.resize(9 + n);
-      put_frame_header((uint8_t*)frame.data(), n, F_DATA, flags, sid);
-      memcpy(&frame[9], payload.data() + off, n);
-      send_raw(frame.data(), frame.size());
+      size_t n = std::min((size_t)avail, total - off);
+      uint8_t hdr[9];
+      put_frame_header(hdr, n, F_DATA, 0, sid);
+      struct iovec iov[3];
+      iov[0].iov_base = hdr;
+      iov[0].iov_len = 9;
+      int cnt = 1 + payload_iov(iov + 1, prefix, msg, off, n);
+      send_iov(iov, cnt);
       {
         std::lock_guard<std::mutex> lk(win_mu_);
         conn_send_window_ -= n;
         stream_window_ref(sid) -= n;
       }
       off += n;
-      if (last) break;
     }
     return true;
   }
 
   void send_headers_frame(uint32_t sid, const uint8_t* block, size_t n, uint8_t flags) {
-    std::string frame;
-    frame.resize(9 + n);
-    put_frame_header((uint8_t*)frame.data(), n, F_HEADERS, flags, sid);
-    memcpy(&frame[9], block, n);
-    send_raw(frame.data(), frame.size());
+    uint8_t hdr[9];
+    put_frame_header(hdr, n, F_HEADERS, flags, sid);
+    struct iovec iov[2] = {{hdr, 9}, {(void*)block, n}};
+    send_iov(iov, 2);
   }
 
   void send_error(uint32_t sid, int code, const std::string& msg) {
@@ -508,45 +674,39 @@ class Connection : public std::enable_shared_from_this<Connection> {
                        FLAG_END_HEADERS | FLAG_END_STREAM);
   }
 
-  void send_unary_response(uint32_t sid, const std::string& message) {
-    std::string payload;
-    payload.resize(5 + message.size());
-    payload[0] = 0;
-    uint32_t len = htonl((uint32_t)message.size());
-    memcpy(&payload[1], &len, 4);
-    memcpy(&payload[5], message.data(), message.size());
+  void send_unary_response(uint32_t sid, const uint8_t* msg, size_t msg_len) {
+    size_t payload_len = 5 + msg_len;
     bool fits;
     {
       std::lock_guard<std::mutex> lk(win_mu_);
-      fits = (int64_t)payload.size() <= conn_send_window_ &&
-             (int64_t)payload.size() <= stream_window_ref(sid) &&
-             payload.size() <= peer_max_frame_;
+      fits = (int64_t)payload_len <= conn_send_window_ &&
+             (int64_t)payload_len <= stream_window_ref(sid) &&
+             payload_len <= peer_max_frame_;
     }
     if (fits) {
-      // one write: headers + data + trailers
-      std::string out;
-      out.resize(9 + sizeof(kRespHdrBlock) + 9 + payload.size() + 9 +
-                 sizeof(kOkTrailerBlock));
-      uint8_t* p = (uint8_t*)out.data();
+      // one write: headers + data + trailers, the message sent in place
+      uint8_t head[9 + sizeof(kRespHdrBlock) + 9 + 5];
+      uint8_t tail[9 + sizeof(kOkTrailerBlock)];
+      uint8_t* p = head;
       put_frame_header(p, sizeof(kRespHdrBlock), F_HEADERS, FLAG_END_HEADERS, sid);
       p += 9;
       memcpy(p, kRespHdrBlock, sizeof(kRespHdrBlock));
       p += sizeof(kRespHdrBlock);
-      put_frame_header(p, payload.size(), F_DATA, 0, sid);
+      put_frame_header(p, payload_len, F_DATA, 0, sid);
       p += 9;
-      memcpy(p, payload.data(), payload.size());
-      p += payload.size();
-      put_frame_header(p, sizeof(kOkTrailerBlock), F_HEADERS,
+      put_grpc_prefix(p, msg_len);
+      put_frame_header(tail, sizeof(kOkTrailerBlock), F_HEADERS,
                        FLAG_END_HEADERS | FLAG_END_STREAM, sid);
-      p += 9;
-      memcpy(p, kOkTrailerBlock, sizeof(kOkTrailerBlock));
-      send_raw(out.data(), out.size());
+      memcpy(tail + 9, kOkTrailerBlock, sizeof(kOkTrailerBlock));
+      struct iovec iov[3] = {{head, sizeof(head)}, {(void*)msg, msg_len},
+                             {tail, sizeof(tail)}};
+      send_iov(iov, 3);
       std::lock_guard<std::mutex> lk(win_mu_);
-      conn_send_window_ -= payload.size();
-      stream_window_ref(sid) -= payload.size();
+      conn_send_window_ -= payload_len;
+      stream_window_ref(sid) -= payload_len;
     } else {
       send_headers_frame(sid, kRespHdrBlock, sizeof(kRespHdrBlock), FLAG_END_HEADERS);
-      send_data(sid, payload, false, /*pump=*/true);
+      send_message(sid, msg, msg_len, /*pump=*/true);
       send_headers_frame(sid, kOkTrailerBlock, sizeof(kOkTrailerBlock),
                          FLAG_END_HEADERS | FLAG_END_STREAM);
     }
@@ -562,17 +722,22 @@ class Connection : public std::enable_shared_from_this<Connection> {
         auto it = streams_.find(sid);
         if (it != streams_.end()) stp = &it->second;
       }
-      if (stp) dispatch(*stp);
+      if (stp) dispatch(*stp, (const uint8_t*)stp->data.data(), stp->data.size());
     }
   }
 
-  std::string first_grpc_message(const std::string& body) {
-    if (body.size() < 5) return std::string();
+  // view of the first gRPC message in `body`; empty when incomplete
+  static void first_grpc_message(const uint8_t* body, size_t n,
+                                 const uint8_t** msg, size_t* msg_len) {
+    *msg = body;
+    *msg_len = 0;
+    if (n < 5) return;
     uint32_t len;
-    memcpy(&len, body.data() + 1, 4);
+    memcpy(&len, body + 1, 4);
     len = ntohl(len);
-    if (5 + (size_t)len > body.size()) return std::string();
-    return body.substr(5, len);
+    if (5 + (size_t)len > n) return;
+    *msg = body + 5;
+    *msg_len = len;
   }
 
   void cancel_ctx(StreamState& st) {
@@ -585,7 +750,9 @@ class Connection : public std::enable_shared_from_this<Connection> {
     st.ctx = py::object();
   }
 
-  void dispatch(StreamState& st) {
+  // `body` is the stream's whole request body: st.data, or a frame view
+  // that is only valid until the handler's bytes object has been built
+  void dispatch(StreamState& st, const uint8_t* body, size_t body_len) {
     auto it = core_->handlers.find(st.path);
     uint32_t sid = st.id;
     if (it == core_->handlers.end()) {
@@ -593,7 +760,9 @@ class Connection : public std::enable_shared_from_this<Connection> {
       erase_stream(sid);
       return;
     }
-    std::string request = first_grpc_message(st.data);
+    const uint8_t* req;
+    size_t req_len;
+    first_grpc_message(body, body_len, &req, &req_len);
     if (it->second.streaming) {
       // streaming handlers run on their own thread. All py::object copies are
       // made AND destroyed under the GIL: the thread owns a heap pack and
@@ -605,7 +774,8 @@ class Connection : public std::enable_shared_from_this<Connection> {
       Pack* pack = nullptr;
       {
         py::gil_scoped_acquire gil;
-        pack = new Pack{it->second.fn, core_->context_factory(), std::move(request)};
+        pack = new Pack{it->second.fn, core_->context_factory(),
+                        std::string((const char*)req, req_len)};
         st.ctx = pack->ctx;
       }
       // the thread must keep the Connection alive: a raw `this` would dangle
@@ -630,8 +800,10 @@ class Connection : public std::enable_shared_from_this<Connection> {
       }).detach();
       return;
     }
-    // unary: inline on the connection thread
-    std::string response;
+    // unary: inline on the connection thread. The response is copied once
+    // into a buffer this connection keeps, so the handler's result can be
+    // dropped under the GIL already held and then sent without it.
+    std::string& response = resp_buf_;
     int err_code = -1;
     std::string err_msg;
     {
@@ -639,7 +811,7 @@ class Connection : public std::enable_shared_from_this<Connection> {
       try {
         py::object ctx = core_->context_factory();
         st.ctx = ctx;
-        py::object result = it->second.fn(py::bytes(request), ctx);
+        py::object result = it->second.fn(py::bytes((const char*)req, req_len), ctx);
         char* rb;
         Py_ssize_t rn;
         if (PyBytes_AsStringAndSize(result.ptr(), &rb, &rn) == 0) {
@@ -656,7 +828,8 @@ class Connection : public std::enable_shared_from_this<Connection> {
       }
     }
     if (err_code >= 0) send_error(sid, err_code, err_msg);
-    else send_unary_response(sid, response);
+    else send_unary_response(sid, (const uint8_t*)response.data(), response.size());
+    cap_retained(response);
     erase_stream(sid);
   }
 
@@ -733,13 +906,8 @@ class Connection : public std::enable_shared_from_this<Connection> {
       }
       if (done) break;
       if (!ok) break;
-      std::string payload;
-      payload.resize(5 + item.size());
-      payload[0] = 0;
-      uint32_t len = htonl((uint32_t)item.size());
-      memcpy(&payload[1], &len, 4);
-      memcpy(&payload[5], item.data(), item.size());
-      if (!send_data(sid, payload, false, /*pump=*/false)) break;
+      if (!send_message(sid, (const uint8_t*)item.data(), item.size(), /*pump=*/false))
+        break;
     }
     {
       // drop the iterator/ctx with the GIL held
@@ -781,8 +949,8 @@ class Connection : public std::enable_shared_from_this<Connection> {
 
   bool expect_preface() {
     if (!fill(24)) return false;
-    bool ok = memcmp(buf_.data() + pos_, "PRI * HTTP/2.0\r\n\r\nSM\r\n\r\n", 24) == 0;
-    pos_ += 24;
+    bool ok = memcmp(buf_.head(), "PRI * HTTP/2.0\r\n\r\nSM\r\n\r\n", 24) == 0;
+    buf_.consume(24);
     return ok;
   }
 
@@ -805,8 +973,8 @@ class Connection : public std::enable_shared_from_this<Connection> {
 
   int fd_;
   std::shared_ptr<CoreShared> core_;
-  std::string buf_;
-  size_t pos_ = 0;
+  RecvBuf buf_;
+  std::string resp_buf_;  // unary response in flight (connection thread only)
   std::atomic<bool> closed_{false};
   HpackDecoder decoder_;
   std::unordered_map<uint32_t, StreamState> streams_;
@@ -972,7 +1140,6 @@ class ClientCore {
       throw std::runtime_error("connect failed: " + path_);
     }
     buf_.clear();
-    pos_ = 0;
     next_stream_ = 1;
     decoder_ = HpackDecoder();
     peer_max_frame_ = 16384;
@@ -1006,20 +1173,35 @@ class ClientCore {
   // returns (grpc_status, response_bytes, grpc_message). Transport failures
   // throw std::runtime_error (Python resets + maps to UNAVAILABLE).
   py::tuple call_unary(py::bytes header_block_b, py::bytes message_b, double timeout_s) {
-    std::string header_block = header_block_b;
-    std::string message = message_b;
+    // the arguments keep both bytes objects alive for the whole call, so the
+    // request is sent from the caller's memory with the GIL released
+    char *hb, *mb;
+    Py_ssize_t hn, mn;
+    if (PyBytes_AsStringAndSize(header_block_b.ptr(), &hb, &hn) != 0 ||
+        PyBytes_AsStringAndSize(message_b.ptr(), &mb, &mn) != 0)
+      throw py::error_already_set();
     int status = 0;
-    std::string data, grpc_message, err;
+    const uint8_t* data = nullptr;
+    size_t data_len = 0;
+    std::string grpc_message, err;
     {
       py::gil_scoped_release release;
       try {
-        do_call(header_block, message, timeout_s, &status, &data, &grpc_message);
+        do_call((const uint8_t*)hb, (size_t)hn, (const uint8_t*)mb, (size_t)mn,
+                timeout_s, &status, &data, &data_len, &grpc_message);
       } catch (const std::exception& e) {
         err = e.what();
       }
     }
-    if (!err.empty()) throw std::runtime_error(err);
-    return py::make_tuple(status, py::bytes(data), grpc_message);
+    if (!err.empty()) {
+      cap_retained(rdata_);
+      throw std::runtime_error(err);
+    }
+    // `data` points into rdata_, which lives until the next call
+    py::tuple out = py::make_tuple(status, py::bytes((const char*)data, data_len),
+                                   grpc_message);
+    cap_retained(rdata_);
+    return out;
   }
 
  private:
@@ -1033,58 +1215,47 @@ class ClientCore {
   }
 
   void write_all(const void* data, size_t n) {
-    const uint8_t* p = (const uint8_t*)data;
-    size_t off = 0;
-    while (off < n) {
-      ssize_t w = ::write(fd_, p + off, n - off);
-      if (w <= 0) throw std::runtime_error("connection lost (write)");
-      off += w;
-    }
+    struct iovec iov{(void*)data, n};
+    writev_all_or_throw(&iov, 1);
+  }
+
+  void writev_all_or_throw(struct iovec* iov, int cnt) {
+    if (!writev_all(fd_, iov, cnt)) throw std::runtime_error("connection lost (write)");
   }
 
   bool fill(size_t need) {
-    while (buf_.size() - pos_ < need) {
-      uint8_t tmp[262144];
-      ssize_t r = ::read(fd_, tmp, sizeof(tmp));
+    while (buf_.avail() < need) {
+      ssize_t r = buf_.read_more(fd_, need);
       if (r == 0) throw std::runtime_error("connection closed");
       if (r < 0) {
+        if (errno == EINTR) continue;
         if (errno == EAGAIN || errno == EWOULDBLOCK)
           throw std::runtime_error("timeout");
         throw std::runtime_error("connection lost (read)");
-      }
-      buf_.append((const char*)tmp, r);
-      if (pos_ > (1 << 20) && pos_ * 2 > buf_.size()) {
-        buf_.erase(0, pos_);
-        pos_ = 0;
       }
     }
     return true;
   }
 
-  void read_frame(uint8_t* type, uint8_t* flags, uint32_t* sid, std::string* body) {
-    fill(9);
-    const uint8_t* h = (const uint8_t*)buf_.data() + pos_;
-    uint32_t len = h[0] << 16 | h[1] << 8 | h[2];
-    *type = h[3];
-    *flags = h[4];
-    uint32_t sraw;
-    memcpy(&sraw, h + 5, 4);
-    *sid = ntohl(sraw) & 0x7fffffff;
-    if (len > 64u * 1024 * 1024) throw std::runtime_error("oversize frame");
-    fill(9 + len);
-    body->assign(buf_.data() + pos_ + 9, len);
-    pos_ += 9 + len;
+  // f->body is a view into buf_ and dies at the next read_frame()
+  void read_frame(Frame* f) {
+    bool oversize;
+    if (!next_frame(buf_, [this](size_t n) { return fill(n); }, f, &oversize))
+      throw std::runtime_error("oversize frame");
   }
 
   // conn-level frames; returns true if consumed
-  bool handle_conn_frame(uint8_t type, uint8_t flags, uint32_t sid,
-                         const std::string& body, int64_t* active_stream_window) {
+  bool handle_conn_frame(const Frame& f, int64_t* active_stream_window) {
+    const uint8_t type = f.type, flags = f.flags;
+    const uint32_t sid = f.sid;
+    const uint8_t* body = f.body;
+    const size_t blen = f.len;
     if (type == F_SETTINGS) {
       if (!(flags & FLAG_ACK)) {
-        for (size_t off = 0; off + 6 <= body.size(); off += 6) {
-          uint16_t k = (uint8_t)body[off] << 8 | (uint8_t)body[off + 1];
+        for (size_t off = 0; off + 6 <= blen; off += 6) {
+          uint16_t k = body[off] << 8 | body[off + 1];
           uint32_t v;
-          memcpy(&v, body.data() + off + 2, 4);
+          memcpy(&v, body + off + 2, 4);
           v = ntohl(v);
           if (k == S_MAX_FRAME) peer_max_frame_ = v;
           else if (k == S_INITIAL_WINDOW) {
@@ -1100,17 +1271,18 @@ class ClientCore {
       return true;
     }
     if (type == F_PING) {
-      if (!(flags & FLAG_ACK) && body.size() == 8) {
+      if (!(flags & FLAG_ACK) && blen == 8) {
         uint8_t p[17];
         put_frame_header(p, 8, F_PING, FLAG_ACK, 0);
-        memcpy(p + 9, body.data(), 8);
+        memcpy(p + 9, body, 8);
         write_all(p, 17);
       }
       return true;
     }
     if (type == F_WINUP && sid == 0) {
+      if (blen != 4) return true;
       uint32_t inc;
-      memcpy(&inc, body.data(), 4);
+      memcpy(&inc, body, 4);
       conn_send_window_ += ntohl(inc) & 0x7fffffff;
       return true;
     }
@@ -1118,41 +1290,42 @@ class ClientCore {
     return false;
   }
 
-  void do_call(const std::string& header_block, const std::string& message,
-               double timeout_s, int* status, std::string* data,
-               std::string* grpc_message) {
+  void do_call(const uint8_t* header_block, size_t header_len, const uint8_t* message,
+               size_t message_len, double timeout_s, int* status,
+               const uint8_t** data, size_t* data_len, std::string* grpc_message) {
     set_timeout(timeout_s);
     uint32_t sid = next_stream_;
     next_stream_ += 2;
     int64_t stream_window = peer_initial_window_;
 
-    std::string payload;
-    payload.resize(5 + message.size());
-    payload[0] = 0;
-    uint32_t mlen = htonl((uint32_t)message.size());
-    memcpy(&payload[1], &mlen, 4);
-    memcpy(&payload[5], message.data(), message.size());
-
-    std::string out;
-    out.resize(9);
-    put_frame_header((uint8_t*)out.data(), header_block.size(), F_HEADERS,
-                     FLAG_END_HEADERS, sid);
-    out += header_block;
-    size_t off = 0, total = payload.size();
+    // HEADERS ride in the first DATA frame's writev; every DATA frame is one
+    // iovec group: frame header, its share of the 5-byte gRPC prefix, and
+    // its share of the caller's bytes in place
+    uint8_t prefix[5];
+    put_grpc_prefix(prefix, message_len);
+    uint8_t hhdr[9];
+    put_frame_header(hhdr, header_len, F_HEADERS, FLAG_END_HEADERS, sid);
+    bool headers_sent = false;
+    size_t off = 0, total = 5 + message_len;
     while (true) {
       int64_t avail = std::min(conn_send_window_, stream_window);
       if ((int64_t)peer_max_frame_ < avail) avail = peer_max_frame_;
-      if (total - off > 0 && avail <= 0) {
-        write_all(out.data(), out.size());
-        out.clear();
-        uint8_t type, flags; uint32_t fsid; std::string body;
-        read_frame(&type, &flags, &fsid, &body);
-        if (!handle_conn_frame(type, flags, fsid, body, &stream_window)) {
-          if (type == F_WINUP && fsid == sid) {
-            uint32_t inc;
-            memcpy(&inc, body.data(), 4);
-            stream_window += ntohl(inc) & 0x7fffffff;
-          } else if (type == F_RST) {
+      if (avail <= 0) {
+        if (!headers_sent) {
+          struct iovec hv[2] = {{hhdr, 9}, {(void*)header_block, header_len}};
+          writev_all_or_throw(hv, 2);
+          headers_sent = true;
+        }
+        Frame f;
+        read_frame(&f);
+        if (!handle_conn_frame(f, &stream_window)) {
+          if (f.type == F_WINUP && f.sid == sid) {
+            if (f.len == 4) {
+              uint32_t inc;
+              memcpy(&inc, f.body, 4);
+              stream_window += ntohl(inc) & 0x7fffffff;
+            }
+          } else if (f.type == F_RST) {
             throw std::runtime_error("stream reset during send");
           }
         }
@@ -1160,32 +1333,43 @@ class ClientCore {
       }
       size_t n = std::min(total - off, (size_t)avail);
       bool last = off + n >= total;
-      uint8_t flags = last ? FLAG_END_STREAM : 0;
-      size_t fo = out.size();
-      out.resize(fo + 9 + n);
-      put_frame_header((uint8_t*)out.data() + fo, n, F_DATA, flags, sid);
-      memcpy(&out[fo + 9], payload.data() + off, n);
+      uint8_t dhdr[9];
+      put_frame_header(dhdr, n, F_DATA, last ? FLAG_END_STREAM : 0, sid);
+      struct iovec iov[5];
+      int cnt = 0;
+      if (!headers_sent) {
+        iov[cnt++] = {hhdr, 9};
+        iov[cnt++] = {(void*)header_block, header_len};
+        headers_sent = true;
+      }
+      iov[cnt++] = {dhdr, 9};
+      cnt += payload_iov(iov + cnt, prefix, message, off, n);
+      writev_all_or_throw(iov, cnt);
       conn_send_window_ -= n;
       stream_window -= n;
       off += n;
       if (last) break;
     }
-    write_all(out.data(), out.size());
 
-    // response
-    std::string rdata;
+    // response: DATA accumulates in a buffer this client keeps
+    std::string& rdata = rdata_;
+    rdata.clear();
     std::vector<std::pair<std::string, std::string>> headers;
     while (true) {
-      uint8_t type, flags; uint32_t fsid; std::string body;
-      read_frame(&type, &flags, &fsid, &body);
-      if (handle_conn_frame(type, flags, fsid, body, &stream_window)) continue;
-      if (fsid != sid) continue;
+      Frame f;
+      read_frame(&f);
+      if (handle_conn_frame(f, &stream_window)) continue;
+      const uint8_t type = f.type, flags = f.flags;
+      const uint8_t* body = f.body;
+      const size_t blen = f.len;
+      if (f.sid != sid) continue;
       if (type == F_HEADERS || type == F_CONT) {
         size_t hoff = 0, pad = 0;
-        if (type == F_HEADERS && (flags & FLAG_PADDED)) { pad = (uint8_t)body[0]; hoff = 1; }
+        if (type == F_HEADERS && (flags & FLAG_PADDED)) { pad = blen ? body[0] : 0; hoff = 1; }
         if (type == F_HEADERS && (flags & FLAG_PRIORITY)) hoff += 5;
-        if (!decoder_.decode((const uint8_t*)body.data() + hoff,
-                             body.size() - hoff - pad, &headers))
+        if (hoff > blen || pad > blen - hoff)
+          throw std::runtime_error("bad hpack from server");
+        if (!decoder_.decode(body + hoff, blen - hoff - pad, &headers))
           throw std::runtime_error("bad hpack from server");
         if (flags & FLAG_END_STREAM) {
           int st = 0;
@@ -1202,23 +1386,26 @@ class ClientCore {
               i += 2;
             } else dec.push_back(msg[i]);
           }
-          // parse first grpc frame of rdata
-          std::string first;
+          // first grpc message of rdata, as a view
+          *data = (const uint8_t*)rdata.data();
+          *data_len = 0;
           if (rdata.size() >= 5) {
             uint32_t len;
             memcpy(&len, rdata.data() + 1, 4);
             len = ntohl(len);
-            if (5 + (size_t)len <= rdata.size()) first = rdata.substr(5, len);
+            if (5 + (size_t)len <= rdata.size()) {
+              *data = (const uint8_t*)rdata.data() + 5;
+              *data_len = len;
+            }
           }
           *status = st;
-          *data = first;
           *grpc_message = dec;
           return;
         }
       } else if (type == F_DATA) {
-        rdata += body;
-        if (!body.empty()) {
-          conn_recv_deficit_ += body.size();
+        rdata.append((const char*)body, blen);
+        if (blen) {
+          conn_recv_deficit_ += blen;
           if (conn_recv_deficit_ >= RECV_WINDOW / 2) {
             uint8_t f2[26];
             put_frame_header(f2, 4, F_WINUP, 0, 0);
@@ -1240,8 +1427,8 @@ class ClientCore {
 
   std::string path_;
   int fd_ = -1;
-  std::string buf_;
-  size_t pos_ = 0;
+  RecvBuf buf_;
+  std::string rdata_;  // response body of the call in flight
   uint32_t next_stream_ = 1;
   HpackDecoder decoder_;
   uint32_t peer_max_frame_ = 16384;

@@ -153,38 +153,29 @@ py::bytes encode_nested_string_lists(const std::vector<std::vector<std::string>>
 // span comparison matches Python's code-point string order because UTF-8 is
 // order-preserving. GIL released during parse/sort/hash.
 
+void sha256_evp(const void* data, size_t len, unsigned char md[32]) {
+  unsigned int mdlen = 0;
+  EVP_Digest(data, len, md, &mdlen, EVP_sha256(), nullptr);
+}
+
+using wirecore::DigestOut;
+using wirecore::DigestScratch;
+using wirecore::ScratchGuard;
+using wirecore::Span;
+
 std::vector<std::pair<std::string, size_t>> digest_raw(const uint8_t* p, size_t len) {
-  std::vector<std::pair<const uint8_t*, size_t>> outer;
+  // container requests are few (one per container); only the per-container
+  // ID walk is hot
+  std::vector<Span> outer;
   field1_spans(p, p + len, outer);
   std::vector<std::pair<std::string, size_t>> result;
   result.reserve(outer.size());
+  DigestScratch& sc = wirecore::digest_scratch();
   for (auto& o : outer) {
-    std::vector<std::pair<const uint8_t*, size_t>> ids;
-    field1_spans(o.first, o.first + o.second, ids);
-    auto cmp = [](const std::pair<const uint8_t*, size_t>& a,
-                  const std::pair<const uint8_t*, size_t>& b) {
-      int c = memcmp(a.first, b.first, std::min(a.second, b.second));
-      if (c) return c < 0;
-      return a.second < b.second;
-    };
-    if (!std::is_sorted(ids.begin(), ids.end(), cmp))
-      std::sort(ids.begin(), ids.end(), cmp);
-    // one-shot hash over a joined buffer: per-span EVP_DigestUpdate calls
-    // cost more than the sha itself at 295k IDs (measured 2.4 ms -> 0.9 ms)
-    std::string joined;
-    size_t total = 0;
-    for (auto& id : ids) total += id.second + 1;
-    joined.reserve(total);
-    for (size_t i = 0; i < ids.size(); ++i) {
-      if (i) joined.push_back(':');
-      joined.append((const char*)ids[i].first, ids[i].second);
-    }
-    unsigned char md[32];
-    unsigned int mdlen = 0;
-    EVP_Digest(joined.data(), joined.size(), md, &mdlen, EVP_sha256(), nullptr);
-    char hex[9];
-    snprintf(hex, sizeof hex, "%02x%02x%02x%02x", md[0], md[1], md[2], md[3]);
-    result.emplace_back(std::string(hex, 8), ids.size());
+    ScratchGuard guard(sc);
+    DigestOut d = wirecore::digest_field(sc, o.first, o.second, 1, false, false,
+                                         sha256_evp);
+    result.emplace_back(std::string(d.hex, 8), d.count);
   }
   return result;
 }
@@ -206,41 +197,23 @@ py::list digest_allocate_request(py::bytes data) {
 
 // PreStartContainerRequest digest: the handler needs the SORTED ID list
 // (persisted in the reference's on-disk record format) plus the device-set
-// hash; one C++ pass sorts the spans, hashes, then materializes the sorted
-// Python strings exactly once.
+// hash; one C++ pass hashes (sorting the spans when kubelet sent them
+// unsorted), then materializes the sorted Python strings exactly once.
 py::tuple decode_prestart_digest(py::bytes data) {
   char* buf;
   Py_ssize_t len;
   PyBytes_AsStringAndSize(data.ptr(), &buf, &len);
-  std::vector<std::pair<const uint8_t*, size_t>> ids;
-  char hex[9];
+  DigestScratch& sc = wirecore::digest_scratch();
+  ScratchGuard guard(sc);
+  DigestOut d;
   {
     py::gil_scoped_release rel;
-    field1_spans((const uint8_t*)buf, (const uint8_t*)buf + len, ids);
-    auto cmp = [](const std::pair<const uint8_t*, size_t>& a,
-                  const std::pair<const uint8_t*, size_t>& b) {
-      int c = memcmp(a.first, b.first, std::min(a.second, b.second));
-      if (c) return c < 0;
-      return a.second < b.second;
-    };
-    if (!std::is_sorted(ids.begin(), ids.end(), cmp))
-      std::sort(ids.begin(), ids.end(), cmp);
-    std::string joined;
-    size_t jtotal = 0;
-    for (auto& id : ids) jtotal += id.second + 1;
-    joined.reserve(jtotal);
-    for (size_t i = 0; i < ids.size(); ++i) {
-      if (i) joined.push_back(':');
-      joined.append((const char*)ids[i].first, ids[i].second);
-    }
-    unsigned char md[32];
-    unsigned int mdlen = 0;
-    EVP_Digest(joined.data(), joined.size(), md, &mdlen, EVP_sha256(), nullptr);
-    snprintf(hex, sizeof hex, "%02x%02x%02x%02x", md[0], md[1], md[2], md[3]);
+    d = wirecore::digest_field(sc, (const uint8_t*)buf, (size_t)len, 1, false, true,
+                               sha256_evp);
   }
   py::list out;
-  for (auto& s : ids) out.append(py::str((const char*)s.first, s.second));
-  return py::make_tuple(out, py::str(hex, 8));
+  for (auto& s : sc.spans) out.append(py::str((const char*)s.first, s.second));
+  return py::make_tuple(out, py::str(d.hex, 8));
 }
 
 // PreStart digest v2: hash + count + the sorted ID list PRE-SERIALIZED as a
@@ -253,67 +226,16 @@ py::tuple decode_prestart_digest2(py::bytes data) {
   char* buf;
   Py_ssize_t len;
   PyBytes_AsStringAndSize(data.ptr(), &buf, &len);
-  std::vector<std::pair<const uint8_t*, size_t>> ids;
-  char hex[9];
-  std::string list_json;
+  DigestScratch& sc = wirecore::digest_scratch();
+  ScratchGuard guard(sc);
+  DigestOut d;
   {
     py::gil_scoped_release rel;
-    field1_spans((const uint8_t*)buf, (const uint8_t*)buf + len, ids);
-    auto cmp = [](const std::pair<const uint8_t*, size_t>& a,
-                  const std::pair<const uint8_t*, size_t>& b) {
-      int c = memcmp(a.first, b.first, std::min(a.second, b.second));
-      if (c) return c < 0;
-      return a.second < b.second;
-    };
-    if (!std::is_sorted(ids.begin(), ids.end(), cmp))
-      std::sort(ids.begin(), ids.end(), cmp);
-    size_t total = 2;
-    for (auto& id : ids) total += id.second + 3;
-    std::string joined;
-    joined.reserve(total);
-    for (size_t i = 0; i < ids.size(); ++i) {
-      if (i) joined.push_back(':');
-      joined.append((const char*)ids[i].first, ids[i].second);
-    }
-    unsigned char md[32];
-    unsigned int mdlen = 0;
-    EVP_Digest(joined.data(), joined.size(), md, &mdlen, EVP_sha256(), nullptr);
-    snprintf(hex, sizeof hex, "%02x%02x%02x%02x", md[0], md[1], md[2], md[3]);
-    // JSON array fragment (json.dumps-equivalent for these strings)
-    list_json.reserve(total + ids.size() / 8);
-    list_json.push_back('[');
-    for (size_t i = 0; i < ids.size(); ++i) {
-      if (i) list_json.push_back(',');
-      list_json.push_back('"');
-      const char* sp = (const char*)ids[i].first;
-      size_t n = ids[i].second, j = 0;
-      while (j < n) {
-        size_t run = j;
-        while (run < n) {
-          uint8_t c = (uint8_t)sp[run];
-          if (c == '"' || c == '\\' || c < 0x20) break;
-          ++run;
-        }
-        list_json.append(sp + j, run - j);  // bulk copy of the clean run
-        j = run;
-        if (j < n) {
-          uint8_t c = (uint8_t)sp[j++];
-          if (c == '"' || c == '\\') {
-            list_json.push_back('\\');
-            list_json.push_back((char)c);
-          } else {
-            char esc[8];
-            snprintf(esc, sizeof esc, "\\u%04x", c);
-            list_json.append(esc);
-          }
-        }
-      }
-      list_json.push_back('"');
-    }
-    list_json.push_back(']');
+    d = wirecore::digest_field(sc, (const uint8_t*)buf, (size_t)len, 1, true, false,
+                               sha256_evp);
   }
-  return py::make_tuple(py::str(hex, 8), (long long)ids.size(),
-                        py::bytes(list_json));
+  return py::make_tuple(py::str(d.hex, 8), (long long)d.count,
+                        py::bytes(sc.json.data(), d.json_len));
 }
 
 // ---- podresources List digest --------------------------------------------
@@ -336,6 +258,7 @@ py::list podresources_digest(py::bytes data) {
   std::vector<Row> rows;
   {
     py::gil_scoped_release rel;
+    DigestScratch& sc = wirecore::digest_scratch();
     auto span_fields = [](const uint8_t* p, const uint8_t* end, uint32_t want,
                           std::vector<std::pair<const uint8_t*, size_t>>& out) {
       Reader r{p, end};
@@ -372,8 +295,9 @@ py::list podresources_digest(py::bytes data) {
         if (!f.empty()) cname.assign((const char*)f[0].first, f[0].second);
         std::vector<std::pair<const uint8_t*, size_t>> devs;
         span_fields(cspan.first, cspan.first + cspan.second, 2, devs);
-        // group ids per resource_name (a container may list a resource in
-        // one ContainerDevices entry pre-1.21 or one entry per ID after)
+        // group the ContainerDevices entries per resource_name (a container
+        // may list a resource in one entry pre-1.21 or one entry per ID
+        // after); the digest walks each group's entries as one ID set
         std::vector<std::pair<std::string,
                               std::vector<std::pair<const uint8_t*, size_t>>>> groups;
         for (auto& dspan : devs) {
@@ -381,45 +305,25 @@ py::list podresources_digest(py::bytes data) {
           span_fields(dspan.first, dspan.first + dspan.second, 1, f);
           std::string res;
           if (!f.empty()) res.assign((const char*)f[0].first, f[0].second);
-          std::vector<std::pair<const uint8_t*, size_t>> ids;
-          span_fields(dspan.first, dspan.first + dspan.second, 2, ids);
           bool found = false;
           for (auto& g : groups)
             if (g.first == res) {
-              g.second.insert(g.second.end(), ids.begin(), ids.end());
+              g.second.push_back(dspan);
               found = true;
               break;
             }
-          if (!found) groups.emplace_back(res, std::move(ids));
+          if (!found)
+            groups.emplace_back(
+                res, std::vector<std::pair<const uint8_t*, size_t>>{dspan});
         }
         for (auto& g : groups) {
-          auto& ids = g.second;
-          if (ids.empty()) continue;
-          auto cmp = [](const std::pair<const uint8_t*, size_t>& a,
-                        const std::pair<const uint8_t*, size_t>& b) {
-            int c = memcmp(a.first, b.first, std::min(a.second, b.second));
-            if (c) return c < 0;
-            return a.second < b.second;
-          };
-          if (!std::is_sorted(ids.begin(), ids.end(), cmp))
-            std::sort(ids.begin(), ids.end(), cmp);
-          std::string joined;
-          size_t total = 0;
-          for (auto& id : ids) total += id.second + 1;
-          joined.reserve(total);
-          for (size_t i = 0; i < ids.size(); ++i) {
-            if (i) joined.push_back(':');
-            joined.append((const char*)ids[i].first, ids[i].second);
-          }
-          unsigned char md[32];
-          unsigned int mdlen = 0;
-          EVP_Digest(joined.data(), joined.size(), md, &mdlen, EVP_sha256(),
-                     nullptr);
-          char hex[9];
-          snprintf(hex, sizeof hex, "%02x%02x%02x%02x", md[0], md[1], md[2],
-                   md[3]);
+          auto& ranges = g.second;
+          ScratchGuard guard(sc);
+          DigestOut d = wirecore::digest_ranges(sc, ranges.data(), ranges.size(), 2,
+                                                false, false, sha256_evp);
+          if (d.count == 0) continue;
           rows.push_back(Row{pod_ns, pod_name, cname, g.first,
-                             std::string(hex, 8), ids.size()});
+                             std::string(d.hex, 8), d.count});
         }
       }
     }

@@ -7,7 +7,8 @@
 //   0: HPACK header-block decode (h2core.h — the code in _etransport)
 //   1: Huffman string decode
 //   2: protobuf wire walk (wirecore.h field1_spans — the code in _fastwire)
-//   3: nested walk like AllocateRequest digest (outer field1 → inner field1)
+//   3: AllocateRequest digest (outer field1 → wirecore.h digest_field per
+//      container: the fused walk/check/join/hash helper behind _fastwire)
 //   4: minijson parse (OCI config/state parsing in egpu-hook)
 //   5: devfilter OCI device-rule extraction + eBPF program build
 //
@@ -50,15 +51,34 @@ void fuzz_wire(const uint8_t* data, size_t size) {
   }
 }
 
+// stand-in for sha256: the harness links no crypto library. It reads every
+// joined byte, so ASan sees any join that ran past its buffer.
+void sum_digest(const void* data, size_t len, unsigned char md[32]) {
+  uint64_t h = 1469598103934665603ull;
+  const uint8_t* p = (const uint8_t*)data;
+  for (size_t i = 0; i < len; ++i) h = (h ^ p[i]) * 1099511628211ull;
+  for (int i = 0; i < 32; ++i) md[i] = (unsigned char)(h >> (8 * (i & 7)));
+}
+
+// the shipped digest: outer field1 -> per container the fused walk / order
+// check / join / hash helper, JSON fragment and sorted spans included
 void fuzz_wire_nested(const uint8_t* data, size_t size) {
   std::vector<std::pair<const uint8_t*, size_t>> outer;
+  wirecore::DigestScratch& sc = wirecore::digest_scratch();
   try {
     wirecore::field1_spans(data, data + size, outer);
     for (auto& o : outer) {
-      std::vector<std::pair<const uint8_t*, size_t>> inner;
-      wirecore::field1_spans(o.first, o.first + o.second, inner);
-      for (auto& i : inner) {
-        if (i.first < data || i.first + i.second > data + size) __builtin_trap();
+      wirecore::ScratchGuard guard(sc);
+      wirecore::DigestOut d = wirecore::digest_field(
+          sc, o.first, o.second, 1, /*want_json=*/true, /*want_spans=*/true, sum_digest);
+      if (d.count != sc.spans.size()) __builtin_trap();
+      if (d.json_len < 2 || d.json_len > sc.json.size()) __builtin_trap();
+      if (sc.json[0] != '[' || sc.json[d.json_len - 1] != ']') __builtin_trap();
+      for (size_t i = 0; i < sc.spans.size(); ++i) {
+        auto& s = sc.spans[i];
+        if (s.first < data || s.first + s.second > data + size) __builtin_trap();
+        // sorted, byte-wise, shorter prefix first
+        if (i && wirecore::span_less(s, sc.spans[i - 1])) __builtin_trap();
       }
     }
   } catch (const std::runtime_error&) {

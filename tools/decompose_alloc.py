@@ -1,32 +1,60 @@
-import os, sys, time, tempfile
+"""Where a large Allocate request's time goes: digest alone vs. the full RPC,
+with the process's minor page faults, system time and voluntary context
+switches per call (getrusage) next to the wall times.
+
+  python tools/decompose_alloc.py              # 18,432 IDs: the mixed config
+  python tools/decompose_alloc.py --ids 73728  # a 72-GiB pod at 1-MiB units
+
+Run from the repository root.
+"""
+import argparse, os, random, resource, sys, time, tempfile
 REPO = os.getcwd()
 sys.path.insert(0, REPO); sys.path.insert(0, os.path.join(REPO, "tests"))
 from elastic_gpu_agent_amd import consts, egrpc, _fastwire
 from elastic_gpu_agent_amd.protos import fastpath, deviceplugin as dp
 from helpers import Harness
 
+ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+ap.add_argument("--ids", type=int, default=18432,
+                help="device IDs in the large request (default: 18432)")
+ap.add_argument("--calls", type=int, default=300, help="timed calls per row")
+ap.add_argument("--no-preferred", action="store_true",
+                help="skip the 295k-pool GetPreferredAllocation row")
+args = ap.parse_args()
+
 tmp = tempfile.mkdtemp(); h = Harness(tmp, gpus=1, mem_unit_mib=1)
 h.plugin.memory_server.serve(); h.plugin.memory_server.wait_ready()
 ch = egrpc.Channel(h.plugin.memory_server.socket_path)
 raw = ch.unary_unary(dp.METHOD_ALLOCATE)
-units = h.plugin.cfg.operator.devices()[0].memory_mib // 4
-ids = [f"0-{i:06d}" for i in range(units)]
+ids = [f"0-{i:06d}" for i in range(args.ids)]
 enc = fastpath.encode_allocate_request({"container_requests":[{"devicesIDs": ids}]})
-def t(label, fn, n=60):
-    fn()
+shuffled = list(ids); random.Random(0).shuffle(shuffled)
+enc_shuf = fastpath.encode_allocate_request({"container_requests":[{"devicesIDs": shuffled}]})
+pre_enc = _fastwire.encode_string_list(ids)
+print(f"{'':42s} {'us':>8s} {'minflt':>8s} {'sys us':>8s} {'user us':>8s} {'vcsw':>6s}   (per call)")
+def t(label, fn, n=args.calls):
+    fn(); fn()
+    r0 = resource.getrusage(resource.RUSAGE_SELF)
     t0=time.perf_counter()
     for _ in range(n): fn()
-    print(f"{label:42s} {(time.perf_counter()-t0)/n*1e6:8.0f} us")
-print("req bytes:", len(enc))
+    dt = time.perf_counter()-t0
+    r1 = resource.getrusage(resource.RUSAGE_SELF)
+    print(f"{label:42s} {dt/n*1e6:8.0f} {(r1.ru_minflt-r0.ru_minflt)/n:8.1f} "
+          f"{(r1.ru_stime-r0.ru_stime)/n*1e6:8.0f} {(r1.ru_utime-r0.ru_utime)/n*1e6:8.0f} "
+          f"{(r1.ru_nvcsw-r0.ru_nvcsw)/n:6.1f}")
+print("ids:", args.ids, " req bytes:", len(enc))
 t("digest_allocate_request (C++ alone)", lambda: _fastwire.digest_allocate_request(enc))
+t("digest_allocate_request, shuffled IDs", lambda: _fastwire.digest_allocate_request(enc_shuf))
+t("decode_prestart_digest2 (C++ alone)", lambda: _fastwire.decode_prestart_digest2(pre_enc))
 t("wire+server full (pre-encoded)", lambda: raw(enc))
-small = fastpath.encode_allocate_request({"container_requests":[{"devicesIDs": ids[:100]}]})
-t("wire+server (100 ids)", lambda: raw(small))
-# GetPreferredAllocation at full 295k pool
-pool = [f"0-{i:06d}" for i in range(295_000)]
-pref_enc = dp.PreferredAllocationRequest.encode({"container_requests":[
-    {"available_deviceIDs": pool, "allocation_size": 73728}]})
-pref_raw = ch.unary_unary(dp.METHOD_GET_PREFERRED_ALLOCATION)
-print("pref req bytes:", len(pref_enc))
-t("GetPreferred wire+server (295k pool)", lambda: pref_raw(pref_enc), n=15)
+small = fastpath.encode_allocate_request({"container_requests":[{"devicesIDs": ids[:20]}]})
+t("wire+server (20 ids)", lambda: raw(small))
+if not args.no_preferred:
+    # GetPreferredAllocation at full 295k pool
+    pool = [f"0-{i:06d}" for i in range(295_000)]
+    pref_enc = dp.PreferredAllocationRequest.encode({"container_requests":[
+        {"available_deviceIDs": pool, "allocation_size": 73728}]})
+    pref_raw = ch.unary_unary(dp.METHOD_GET_PREFERRED_ALLOCATION)
+    print("pref req bytes:", len(pref_enc))
+    t("GetPreferred wire+server (295k pool)", lambda: pref_raw(pref_enc), n=15)
 ch.close(); h.close()

@@ -6,6 +6,7 @@ Usage:
   python -m elastic_gpu_agent_amd.native.build_fuzz --run 60    # fuzz 60 s
   python -m elastic_gpu_agent_amd.native.build_fuzz --replay    # in-tree corpus, once
   python -m elastic_gpu_agent_amd.native.build_fuzz --selftest  # ASan+UBSan digest cases
+                                                                # (general, then fixed-stride/radix)
 """
 from __future__ import annotations
 
@@ -52,15 +53,15 @@ def replay(binary, corpus=None):
     return subprocess.call(cmd)
 
 
-def build_selftest(out=None):
+def build_selftest(out=None, source="digest_selftest.cpp"):
     """digest_selftest.cpp: wirecore.h's fused digest against a naive
     reference, as an ordinary program with ASan + UBSan (no fuzzer runtime)."""
     out = out or os.path.join(REPO, "bin", "egpu-digest-selftest")
     os.makedirs(os.path.dirname(out), exist_ok=True)
     cmd = [
-        CLANGXX, "-O1", "-g", "-std=c++17",
+        CLANGXX, "-O1", "-g", "-std=c++17", "-pthread",
         "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-        os.path.join(HERE, "digest_selftest.cpp"),
+        os.path.join(HERE, source),
         "-I", HERE, "-o", out,
     ]
     print("+", " ".join(cmd), flush=True)
@@ -68,9 +69,17 @@ def build_selftest(out=None):
     return out
 
 
+def build_stride_selftest(out=None):
+    """digest_stride_selftest.cpp: the fixed-stride run and the radix
+    fallback of the same digest, built the same way."""
+    out = out or os.path.join(REPO, "bin", "egpu-digest-stride-selftest")
+    return build_selftest(out, "digest_stride_selftest.cpp")
+
+
 if __name__ == "__main__":
     if "--selftest" in sys.argv:
-        sys.exit(subprocess.call([build_selftest()]))
+        rc = subprocess.call([build_selftest()])
+        sys.exit(rc or subprocess.call([build_stride_selftest()]))
     binary = build()
     if "--replay" in sys.argv:
         sys.exit(replay(binary))

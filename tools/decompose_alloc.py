@@ -1,13 +1,15 @@
 """Where a large Allocate request's time goes: digest alone vs. the full RPC,
 with the process's minor page faults, system time and voluntary context
-switches per call (getrusage) next to the wall times.
+switches per call (getrusage) next to the wall times. The sha256 row (hashlib
+over the joined IDs) is the floor of the digest rows; the shuffled rows are
+what kubelet's unsorted lists cost.
 
   python tools/decompose_alloc.py              # 18,432 IDs: the mixed config
   python tools/decompose_alloc.py --ids 73728  # a 72-GiB pod at 1-MiB units
 
 Run from the repository root.
 """
-import argparse, os, random, resource, sys, time, tempfile
+import argparse, hashlib, os, random, resource, sys, time, tempfile
 REPO = os.getcwd()
 sys.path.insert(0, REPO); sys.path.insert(0, os.path.join(REPO, "tests"))
 from elastic_gpu_agent_amd import consts, egrpc, _fastwire
@@ -31,6 +33,8 @@ enc = fastpath.encode_allocate_request({"container_requests":[{"devicesIDs": ids
 shuffled = list(ids); random.Random(0).shuffle(shuffled)
 enc_shuf = fastpath.encode_allocate_request({"container_requests":[{"devicesIDs": shuffled}]})
 pre_enc = _fastwire.encode_string_list(ids)
+pre_enc_shuf = _fastwire.encode_string_list(shuffled)
+joined = ":".join(ids).encode()  # what the digest hashes: the floor of both digest rows
 print(f"{'':42s} {'us':>8s} {'minflt':>8s} {'sys us':>8s} {'user us':>8s} {'vcsw':>6s}   (per call)")
 def t(label, fn, n=args.calls):
     fn(); fn()
@@ -43,9 +47,11 @@ def t(label, fn, n=args.calls):
           f"{(r1.ru_stime-r0.ru_stime)/n*1e6:8.0f} {(r1.ru_utime-r0.ru_utime)/n*1e6:8.0f} "
           f"{(r1.ru_nvcsw-r0.ru_nvcsw)/n:6.1f}")
 print("ids:", args.ids, " req bytes:", len(enc))
+t("sha256 of the joined bytes alone", lambda: hashlib.sha256(joined).hexdigest())
 t("digest_allocate_request (C++ alone)", lambda: _fastwire.digest_allocate_request(enc))
 t("digest_allocate_request, shuffled IDs", lambda: _fastwire.digest_allocate_request(enc_shuf))
 t("decode_prestart_digest2 (C++ alone)", lambda: _fastwire.decode_prestart_digest2(pre_enc))
+t("decode_prestart_digest2, shuffled IDs", lambda: _fastwire.decode_prestart_digest2(pre_enc_shuf))
 t("wire+server full (pre-encoded)", lambda: raw(enc))
 small = fastpath.encode_allocate_request({"container_requests":[{"devicesIDs": ids[:20]}]})
 t("wire+server (20 ids)", lambda: raw(small))

@@ -41,6 +41,13 @@ def main(argv=None) -> int:
     parser.add_argument("--workers", type=int, default=0,
                         help="pre-forked data-plane worker processes accepting "
                              "on the plugin sockets (0 = serve in-process)")
+    parser.add_argument("--gpu-selftest-seconds", type=float, default=0.0,
+                        help="run the active GPU self-test on every GPU this "
+                             "often; a failing GPU is advertised Unhealthy "
+                             "until `egpuctl health IDX --clear` (0 = off)")
+    parser.add_argument("--gpu-selftest-timeout", type=float, default=10.0,
+                        help="time limit of one self-test probe; a probe that "
+                             "exceeds it makes its GPU Unhealthy")
     # path overrides (defaults match the DaemonSet mounts; overridable for
     # local runs and tests)
     parser.add_argument("--plugin-dir", default=None, help="kubelet device-plugins dir")
@@ -92,6 +99,8 @@ def main(argv=None) -> int:
         ),
         metrics_port=args.metrics_port,
         workers=args.workers,
+        selftest_seconds=args.gpu_selftest_seconds,
+        selftest_timeout=args.gpu_selftest_timeout,
     )
     manager = GPUManager(opts)
     manager.run()

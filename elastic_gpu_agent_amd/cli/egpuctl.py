@@ -11,6 +11,10 @@ Subcommands:
                           Unhealthy); --wait blocks until empty; --repartition
                           then flips the partition and undrains
   undrain IDX             return a drained GPU to service
+  health [IDX [--run [--full] | --clear]]
+                          list GPU self-test records; --run probes the GPU now
+                          (same runner and policy as the agent); --clear puts
+                          an unhealthy GPU back in service
   migrate --from BOLT_DB  import a reference agent's BoltDB state
 
 (GC runs inside the agent daemon — event-driven + 60 s timer; there is no
@@ -152,6 +156,39 @@ def cmd_undrain(args) -> int:
     return 0
 
 
+def cmd_health(args) -> int:
+    from ..isolation import health
+    from ..storage import Storage
+
+    st = Storage(args.db)
+    try:
+        if args.index is None:
+            if args.run or args.clear:
+                print("health: --run and --clear need a GPU index", file=sys.stderr)
+                return 2
+            print(json.dumps(health.list_health(st), indent=2))
+            return 0
+        if args.clear:
+            health.clear_health(st, args.index)
+            print(f"gpu {args.index} self-test record cleared "
+                  "(agent re-advertises on its next refresh)")
+            return 0
+        if args.run:
+            # same runner and same policy as the agent's monitor; an operator's
+            # explicit run also probes a GPU that is already unhealthy, but a
+            # pass does not heal it (only --clear does)
+            result = health.subprocess_runner(args.index, args.timeout, full=args.full)
+            rec = health.apply_result(st, args.index, result)
+            print(json.dumps({k: v for k, v in rec.items() if k != "became_unhealthy"},
+                             indent=2))
+            return 0 if rec["passed"] else 1
+        rec = health.get_health(st, args.index)
+        print(json.dumps({str(args.index): rec} if rec else {}, indent=2))
+        return 0
+    finally:
+        st.close()
+
+
 def cmd_migrate(args) -> int:
     from ..storage import Storage, migrate_from_bolt
 
@@ -211,6 +248,21 @@ def main(argv=None) -> int:
     ud = sub.add_parser("undrain", help="return a drained GPU to service")
     ud.add_argument("index", type=int)
     ud.set_defaults(fn=cmd_undrain)
+    he = sub.add_parser(
+        "health",
+        help="list GPU self-test records; probe a GPU now; clear a record",
+    )
+    he.add_argument("index", type=int, nargs="?", default=None)
+    he.add_argument("--run", action="store_true",
+                    help="probe the GPU now and record the result; exits "
+                         "non-zero when the probe fails")
+    he.add_argument("--full", action="store_true",
+                    help="with --run: whole-LDS, 1 GiB probe for a drained or idle GPU")
+    he.add_argument("--clear", action="store_true",
+                    help="forget the record: the GPU is advertised Healthy and probed again")
+    he.add_argument("--timeout", type=float, default=60.0,
+                    help="with --run: time limit of the probe")
+    he.set_defaults(fn=cmd_health)
     pt = sub.add_parser("partition", help="get/set SPX|DPX|QPX|CPX compute partition")
     pt.add_argument("index", type=int)
     pt.add_argument("mode", nargs="?", default=None,

@@ -39,6 +39,10 @@ class ManagerOptions:
     # sockets (kernel load-balancing); 0 = serve in-process. The parent
     # keeps registration, fsnotify watching, GC, Restore and drains.
     workers: int = 0
+    # active GPU self-test (isolation/health.py): seconds between passes over
+    # the GPUs, 0 = off; and the time limit of one probe child
+    selftest_seconds: float = 0.0
+    selftest_timeout: float = 10.0
 
     def to_json(self) -> str:
         import dataclasses
@@ -57,7 +61,8 @@ class ManagerOptions:
 
 
 class GPUManager:
-    def __init__(self, opts: ManagerOptions, sitter=None, locators=None, storage=None):
+    def __init__(self, opts: ManagerOptions, sitter=None, locators=None, storage=None,
+                 selftest_runner=None):
         if opts.gpu_plugin_name != "gpushare":
             raise ValueError(f"unsupported plugin {opts.gpu_plugin_name!r} (only 'gpushare')")
         self.opts = opts
@@ -142,6 +147,8 @@ class GPUManager:
         )
         self.plugin = GPUSharePlugin(self.config)
         self._gc_thread: Optional[threading.Thread] = None
+        self._selftest_runner = selftest_runner
+        self.health_monitor = None
 
     def _on_pod_delete(self, pod) -> None:
         # only pods the scheduler assumed can hold allocations
@@ -171,6 +178,28 @@ class GPUManager:
             from .metrics import GLOBAL_METRICS
 
             GLOBAL_METRICS.serve_prometheus(self.opts.metrics_port)
+        if self.opts.selftest_seconds > 0:
+            self._start_health_monitor()
+
+    def _start_health_monitor(self) -> None:
+        """Parent only (agent workers never call run()): one monitor per
+        node, its verdicts reach the workers through the shared state DB."""
+        from .isolation.health import HealthMonitor, subprocess_runner
+
+        def refresh():
+            self.plugin.core.trigger_refresh()
+            self.plugin.memory.trigger_refresh()
+
+        self.health_monitor = HealthMonitor(
+            self.storage, self.operator,
+            self._selftest_runner or subprocess_runner,
+            self.opts.selftest_seconds,
+            on_change=refresh,
+            event_sink=self.config.event_sink,
+            limits=self.config.limits,
+            timeout=self.opts.selftest_timeout,
+        )
+        self.health_monitor.start()
 
     def _spawn_one_worker(self, core_fd: int, mem_fd: int):
         import subprocess
@@ -219,6 +248,8 @@ class GPUManager:
         return self.plugin.restore()
 
     def stop(self) -> None:
+        if self.health_monitor is not None:
+            self.health_monitor.stop()
         ws = getattr(self, "_worker_stop", None)
         if ws is not None:
             ws.set()

@@ -12,6 +12,10 @@ import time
 from typing import Dict, List, Optional
 
 
+# recorder of the wall time of each GPU self-test probe (isolation/health.py)
+GPU_SELFTEST = "gpu_selftest"
+
+
 class LatencyRecorder:
     """Fixed-size ring of recent latencies (seconds) + running count."""
 

@@ -99,13 +99,14 @@ def build_shim(force=False):
 
 
 def build_kernels(force=False):
-    src = os.path.join(HERE, "egpu_kernels.hip")
+    srcs = [os.path.join(HERE, "egpu_kernels.hip"), os.path.join(HERE, "egpu_selftest.hip")]
+    hdr = os.path.join(HERE, "selftest_ref.h")
     out = os.path.join(PKG, "libegpu_kernels.so")
-    if not force and _newer(out, src):
+    if not force and _newer(out, *srcs, hdr):
         return out
     hipcc = os.path.join(ROCM, "bin", "hipcc")
     _run(
-        [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", src,
+        [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", *srcs,
          "-o", out]
     )
     return out

@@ -1,12 +1,14 @@
 """Build + (optionally) run the libFuzzer harness over the native parsers,
-and the stand-alone sanitizer self-test of the device-set digest.
+and the stand-alone sanitizer self-tests of the device-set digest and of the
+GPU self-test's host reference.
 
 Usage:
   python -m elastic_gpu_agent_amd.native.build_fuzz             # build only
   python -m elastic_gpu_agent_amd.native.build_fuzz --run 60    # fuzz 60 s
   python -m elastic_gpu_agent_amd.native.build_fuzz --replay    # in-tree corpus, once
   python -m elastic_gpu_agent_amd.native.build_fuzz --selftest  # ASan+UBSan digest cases
-                                                                # (general, then fixed-stride/radix)
+                                                                # (general, then fixed-stride/radix),
+                                                                # then selftest_ref.h
 """
 from __future__ import annotations
 
@@ -76,10 +78,18 @@ def build_stride_selftest(out=None):
     return build_selftest(out, "digest_stride_selftest.cpp")
 
 
+def build_ref_selftest(out=None):
+    """selftest_ref_selftest.cpp: the host reference of the GPU self-test
+    (selftest_ref.h, no GPU code), built the same way."""
+    out = out or os.path.join(REPO, "bin", "egpu-selftest-ref-selftest")
+    return build_selftest(out, "selftest_ref_selftest.cpp")
+
+
 if __name__ == "__main__":
     if "--selftest" in sys.argv:
         rc = subprocess.call([build_selftest()])
-        sys.exit(rc or subprocess.call([build_stride_selftest()]))
+        rc = rc or subprocess.call([build_stride_selftest()])
+        sys.exit(rc or subprocess.call([build_ref_selftest()]))
     binary = build()
     if "--replay" in sys.argv:
         sys.exit(replay(binary))

@@ -35,7 +35,8 @@
     }                                                      \
   } while (0)
 
-static char g_err[512] = {0};
+// one error buffer for the whole library (egpu_selftest.hip writes it too)
+__attribute__((visibility("hidden"))) char g_err[512] = {0};
 
 extern "C" const char* egpu_last_error() { return g_err; }
 

@@ -56,8 +56,22 @@ class GPUSharePluginBase:
             log.error("drain flags unreadable: %s", e)
             return set()
 
+    def _unschedulable(self) -> set:
+        """GPUs advertised Unhealthy one by one: operator drains, and GPUs
+        whose self-test record is `unhealthy` (isolation/health.py)."""
+        out = self._drained()
+        if self.cfg.storage is None:
+            return out
+        from ..isolation.health import unhealthy_indexes
+
+        try:
+            return out | unhealthy_indexes(self.cfg.storage)
+        except Exception as e:  # as with drains: never kill ListAndWatch
+            log.error("health records unreadable: %s", e)
+            return out
+
     def list_devices(self, healthy: bool = True) -> List[dict]:
-        drained = self._drained()
+        drained = self._unschedulable()
         out = []
         for gpu in self.cfg.operator.devices():
             health = (
@@ -74,7 +88,7 @@ class GPUSharePluginBase:
         """[(ids, encoded Device suffix)] per GPU — the fast-encode shape."""
         from ..protos import fastpath
 
-        drained = self._drained()
+        drained = self._unschedulable()
         groups = []
         for gpu in self.cfg.operator.devices():
             health = (

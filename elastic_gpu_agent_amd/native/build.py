@@ -76,7 +76,8 @@ def build_etransport(force=False):
         _run([sys.executable, gen])
     ext = sysconfig.get_config_var("EXT_SUFFIX")
     out = os.path.join(PKG, f"_etransport{ext}")
-    if not force and _newer(out, src, tables, os.path.join(HERE, "h2core.h")):
+    headers = [os.path.join(HERE, h) for h in ("h2core.h", "h2frame.h")]
+    if not force and _newer(out, src, tables, *headers):
         return out
     _run(
         ["g++", "-O2", "-g", "-std=c++17", "-shared", "-fPIC", src]

@@ -1,6 +1,6 @@
 """Build + (optionally) run the libFuzzer harness over the native parsers,
-and the stand-alone sanitizer self-tests of the device-set digest and of the
-GPU self-test's host reference.
+and the stand-alone sanitizer self-tests of the device-set digest, of the
+GPU self-test's host reference and of the transport's HTTP/2 framing core.
 
 Usage:
   python -m elastic_gpu_agent_amd.native.build_fuzz             # build only
@@ -8,7 +8,8 @@ Usage:
   python -m elastic_gpu_agent_amd.native.build_fuzz --replay    # in-tree corpus, once
   python -m elastic_gpu_agent_amd.native.build_fuzz --selftest  # ASan+UBSan digest cases
                                                                 # (general, then fixed-stride/radix),
-                                                                # then selftest_ref.h
+                                                                # then selftest_ref.h,
+                                                                # then h2frame.h
 """
 from __future__ import annotations
 
@@ -85,11 +86,20 @@ def build_ref_selftest(out=None):
     return build_selftest(out, "selftest_ref_selftest.cpp")
 
 
+def build_h2frame_selftest(out=None):
+    """h2frame_selftest.cpp: the transport's receive buffer, frame parser and
+    header-block builders (h2frame.h, no Python) over a socketpair, built the
+    same way."""
+    out = out or os.path.join(REPO, "bin", "egpu-h2frame-selftest")
+    return build_selftest(out, "h2frame_selftest.cpp")
+
+
 if __name__ == "__main__":
     if "--selftest" in sys.argv:
         rc = subprocess.call([build_selftest()])
         rc = rc or subprocess.call([build_stride_selftest()])
-        sys.exit(rc or subprocess.call([build_ref_selftest()]))
+        rc = rc or subprocess.call([build_ref_selftest()])
+        sys.exit(rc or subprocess.call([build_h2frame_selftest()]))
     binary = build()
     if "--replay" in sys.argv:
         sys.exit(replay(binary))

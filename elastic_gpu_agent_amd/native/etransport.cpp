@@ -18,12 +18,16 @@
 #include <algorithm>
 #include <arpa/inet.h>
 #include <atomic>
+#include <cerrno>
 #include <condition_variable>
 #include <cstdint>
+#include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <deque>
 #include <memory>
 #include <mutex>
+#include <new>
 #include <string>
 #include <csignal>
 #include <execinfo.h>
@@ -41,248 +45,48 @@ namespace py = pybind11;
 
 namespace {
 
-// ---------------------------------------------------------------- constants
-constexpr uint8_t F_DATA = 0x0, F_HEADERS = 0x1, F_PRIORITY = 0x2, F_RST = 0x3,
-                  F_SETTINGS = 0x4, F_PING = 0x6, F_GOAWAY = 0x7, F_WINUP = 0x8,
-                  F_CONT = 0x9;
-constexpr uint8_t FLAG_END_STREAM = 0x1, FLAG_ACK = 0x1, FLAG_END_HEADERS = 0x4,
-                  FLAG_PADDED = 0x8, FLAG_PRIORITY = 0x20;
-constexpr uint16_t S_HEADER_TABLE_SIZE = 0x1, S_MAX_CONCURRENT = 0x3,
-                   S_INITIAL_WINDOW = 0x4, S_MAX_FRAME = 0x5;
-constexpr int64_t DEFAULT_WINDOW = 65535;
-constexpr int64_t RECV_WINDOW = 32ll * 1024 * 1024;
-constexpr uint32_t OUR_MAX_FRAME = 1024 * 1024;
+// The pybind-free byte work: frames, buffers, header blocks (h2frame.h),
+// HPACK and Huffman (h2core.h, which it includes). Included inside the
+// unnamed namespace, as h2core.h always was here: every system header the
+// two need is already in above, so only their own code lands here, with
+// internal linkage. The module then exports none of it, nothing in the
+// process can interpose it, and the hot-path calls (read_more, HPACK
+// decode) stay direct and inlinable instead of going through the PLT.
+#include "h2frame.h"
 
-// precomputed response blocks (mirror egrpc/server.py: :status 200 indexed,
-// content-type literal w/ static name index 31; grpc-status literal)
-static const uint8_t kRespHdrBlock[] = {
-    0x88, 0x0f, 0x10, 16, 'a','p','p','l','i','c','a','t','i','o','n','/','g','r','p','c'};
-static const uint8_t kOkTrailerBlock[] = {
-    0x00, 0x0b, 'g','r','p','c','-','s','t','a','t','u','s', 0x01, '0'};
-
-#include "h2core.h"
-
+using namespace h2frame;
 using h2core::HpackDecoder;
-using h2core::huffman_decode;
 using h2core::trie_init;
 
-// ---------------------------------------------------------------- helpers
-void put_frame_header(uint8_t* p, uint32_t len, uint8_t type, uint8_t flags,
-                      uint32_t sid) {
-  p[0] = len >> 16; p[1] = len >> 8; p[2] = len;
-  p[3] = type; p[4] = flags;
-  uint32_t s = htonl(sid);
-  memcpy(p + 5, &s, 4);
-}
-
-std::string percent_encode(const std::string& msg) {
-  std::string out;
-  for (unsigned char c : msg) {
-    if (c >= 0x20 && c <= 0x7e && c != '%') out.push_back(c);
-    else {
-      char buf[4];
-      snprintf(buf, sizeof(buf), "%%%02X", c);
-      out += buf;
-    }
-  }
-  return out;
-}
-
-void hpack_put_int(std::string* out, uint64_t v, int prefix, uint8_t flags) {
-  uint64_t limit = (1u << prefix) - 1;
-  if (v < limit) { out->push_back((char)(flags | v)); return; }
-  out->push_back((char)(flags | limit));
-  v -= limit;
-  while (v >= 128) { out->push_back((char)(0x80 | (v & 0x7f))); v >>= 7; }
-  out->push_back((char)v);
-}
-
-// grpc-status + grpc-message literals only — NO pseudo-headers. Used both
-// as a trailers-only response (prefixed by status_prefix_block) and as real
-// trailers after response HEADERS already went out: a :status in trailers
-// is a protocol error to strict HTTP/2 clients (grpc-go kubelet) and
-// escalates an application error into connection teardown (advisor
-// finding, round 1 — this is the native twin of the egrpc/server.py fix).
-std::string status_trailer_fields(int code, const std::string& message) {
-  std::string out;
-  std::string code_s = std::to_string(code);
-  out.push_back((char)0x00);
-  std::string n1 = "grpc-status";
-  hpack_put_int(&out, n1.size(), 7, 0);
-  out += n1;
-  hpack_put_int(&out, code_s.size(), 7, 0);
-  out += code_s;
-  std::string msg = percent_encode(message);
-  out.push_back((char)0x00);
-  std::string n2 = "grpc-message";
-  hpack_put_int(&out, n2.size(), 7, 0);
-  out += n2;
-  hpack_put_int(&out, msg.size(), 7, 0);
-  out += msg;
-  return out;
-}
-
-// :status 200 + content-type prefix for a trailers-only error response
-// (no HEADERS were sent yet for this stream)
-std::string error_trailer_block(int code, const std::string& message) {
-  std::string out;
-  out.push_back((char)0x88);
-  out += std::string("\x0f\x10", 2);
-  std::string ct = "application/grpc";
-  hpack_put_int(&out, ct.size(), 7, 0);
-  out += ct;
-  out += status_trailer_fields(code, message);
-  return out;
-}
-
-// ---------------------------------------------------------------- buffers
-// Receive buffer shared by the server connection and the client: read()
-// lands directly in its tail and frames are handed out as views into it, so
-// a warm connection neither allocates nor copies per request. Capacity is
-// kept across requests; above kRetainCap (one huge ListAndWatch snapshot or
-// GetPreferredAllocation pool) it is given back once the traffic is small
-// again.
-//
-// A view handed out by head() dies at the next read_more(): that call may
-// overwrite, move or reallocate the storage.
-class RecvBuf {
- public:
-  static constexpr size_t kInitCap = 256 * 1024;
-  static constexpr size_t kMinRead = 64 * 1024;
-  static constexpr size_t kRetainCap = 4u << 20;
-
-  RecvBuf() = default;
-  RecvBuf(const RecvBuf&) = delete;
-  RecvBuf& operator=(const RecvBuf&) = delete;
-  ~RecvBuf() { free(data_); }
-
-  size_t avail() const { return end_ - pos_; }
-  const uint8_t* head() const { return data_ + pos_; }
-  void consume(size_t n) { pos_ += n; }
-  void clear() { pos_ = end_ = 0; }
-
-  // one read() into the tail, after making room for `need` contiguous
-  // bytes from head(); returns what read() returned
-  ssize_t read_more(int fd, size_t need) {
-    size_t live = end_ - pos_;
-    if (live == 0) pos_ = end_ = 0;
-    size_t room = std::max(need > live ? need - live : (size_t)0, kMinRead);
-    size_t req = live + room;
-    if (cap_ > kRetainCap && req <= kRetainCap / 2) {
-      reallocate(std::max(req, kInitCap));
-    } else if (cap_ - end_ < room) {
-      // compact only when the consumed prefix dominates; otherwise grow
-      if (pos_ > 0 && pos_ >= live) {
-        memmove(data_, data_ + pos_, live);
-        pos_ = 0;
-        end_ = live;
-      }
-      if (cap_ - end_ < room)
-        reallocate(std::max({live + room, cap_ * 2, kInitCap}));
-    }
-    ssize_t r = ::read(fd, data_ + end_, cap_ - end_);
-    if (r > 0) end_ += (size_t)r;
-    return r;
-  }
-
- private:
-  // new storage holding only the live bytes, at the front
-  void reallocate(size_t ncap) {
-    size_t live = end_ - pos_;
-    uint8_t* n = (uint8_t*)malloc(ncap);
-    if (!n) throw std::bad_alloc();
-    if (live) memcpy(n, data_ + pos_, live);
-    free(data_);
-    data_ = n;
-    cap_ = ncap;
-    pos_ = 0;
-    end_ = live;
-  }
-
-  uint8_t* data_ = nullptr;
-  size_t cap_ = 0, pos_ = 0, end_ = 0;
+// gRPC status of a failed call; default-constructed it is "none"
+struct Status {
+  Status() = default;
+  Status(int c, std::string m) : failed(true), code(c), message(std::move(m)) {}
+  bool failed = false;
+  int code = 0;
+  std::string message;
 };
 
-// one received frame; `body` points into a RecvBuf (see the lifetime note)
-struct Frame {
-  uint8_t type = 0, flags = 0;
-  uint32_t sid = 0;
-  const uint8_t* body = nullptr;
-  size_t len = 0;
-};
+// GIL held. Copies a Python bytes object into *out; anything else is
+// status 13 (INTERNAL) with the text `what`.
+Status take_bytes(py::handle obj, std::string* out, const char* what) {
+  char* rb;
+  Py_ssize_t rn;
+  if (PyBytes_AsStringAndSize(obj.ptr(), &rb, &rn) == 0) {
+    out->assign(rb, rn);
+    return {};
+  }
+  PyErr_Clear();
+  return {13, what};
+}
 
-// parse the frame at the buffer head once `fill` has made it contiguous;
-// fill(n) returns false (server) or throws (client) on I/O failure
-template <class Fill>
-bool next_frame(RecvBuf& buf, Fill&& fill, Frame* f, bool* oversize) {
-  *oversize = false;
-  if (!fill(9)) return false;
-  const uint8_t* h = buf.head();
-  uint32_t len = h[0] << 16 | h[1] << 8 | h[2];
-  f->type = h[3];
-  f->flags = h[4];
-  uint32_t s;
-  memcpy(&s, h + 5, 4);
-  f->sid = ntohl(s) & 0x7fffffff;
-  if (len > 64u * 1024 * 1024) { *oversize = true; return false; }  // refuse absurd frames
-  if (!fill(9 + (size_t)len)) return false;
-  f->body = buf.head() + 9;  // re-read: the second fill may have moved it
-  f->len = len;
-  buf.consume(9 + (size_t)len);
+// false when the path does not fit a sockaddr_un
+bool unix_addr(const std::string& path, sockaddr_un* addr) {
+  *addr = sockaddr_un{};
+  addr->sun_family = AF_UNIX;
+  if (path.size() >= sizeof(addr->sun_path)) return false;
+  strcpy(addr->sun_path, path.c_str());
   return true;
-}
-
-// writev() until every byte is out; the iovec array is consumed
-bool writev_all(int fd, struct iovec* iov, int cnt) {
-  while (cnt > 0) {
-    ssize_t w = ::writev(fd, iov, cnt);
-    if (w <= 0) {
-      if (w < 0 && errno == EINTR) continue;
-      return false;
-    }
-    size_t left = (size_t)w;
-    while (cnt > 0 && left >= iov->iov_len) {
-      left -= iov->iov_len;
-      ++iov;
-      --cnt;
-    }
-    if (cnt > 0 && left) {
-      iov->iov_base = (uint8_t*)iov->iov_base + left;
-      iov->iov_len -= left;
-    }
-  }
-  return true;
-}
-
-// iovecs for bytes [off, off+n) of the logical payload prefix5 ++ msg
-int payload_iov(struct iovec* iov, const uint8_t* prefix5, const uint8_t* msg,
-                size_t off, size_t n) {
-  int k = 0;
-  if (off < 5 && n) {
-    size_t m = std::min(n, 5 - off);
-    iov[k].iov_base = (void*)(prefix5 + off);
-    iov[k].iov_len = m;
-    ++k;
-    off += m;
-    n -= m;
-  }
-  if (n) {
-    iov[k].iov_base = (void*)(msg + (off - 5));
-    iov[k].iov_len = n;
-    ++k;
-  }
-  return k;
-}
-
-void put_grpc_prefix(uint8_t* p, size_t msg_len) {
-  p[0] = 0;
-  uint32_t len = htonl((uint32_t)msg_len);
-  memcpy(p + 1, &len, 4);
-}
-
-// keep a reused string's capacity bounded (same policy as RecvBuf)
-void cap_retained(std::string& s) {
-  if (s.capacity() > RecvBuf::kRetainCap) std::string().swap(s);
 }
 
 // ---------------------------------------------------------------- streams
@@ -346,25 +150,34 @@ class Connection : public std::enable_shared_from_this<Connection> {
     finish();
   }
 
+  // Runs `body` on a detached thread that is counted in live_threads (what
+  // stop() drains) and keeps `conn` alive: a raw pointer would dangle once
+  // the client disconnects and the server prunes the connection. `after`
+  // runs once body is over, but not when the thread is being unwound.
+  template <class Body, class After>
+  static void launch_counted(std::shared_ptr<Connection> conn, Body body, After after) {
+    conn->core_->live_threads.fetch_add(1);
+    auto core = conn->core_;
+    std::thread([conn, core, body, after]() {
+      try {
+        body();
+      } catch (abi::__forced_unwind&) {
+        core->live_threads.fetch_sub(1);
+        throw;  // pthread_exit (interpreter finalization)
+      } catch (...) {
+        // a stray exception in a detached thread would std::terminate the
+        // whole process; drop the connection instead
+        conn->close_now();
+      }
+      after();
+      core->live_threads.fetch_sub(1);
+    }).detach();
+  }
+
   void run_inner() {
     if (!expect_preface()) { return; }
-    {
-      // our SETTINGS + connection window grant
-      uint8_t out[9 + 18 + 13];
-      uint8_t* p = out;
-      put_frame_header(p, 18, F_SETTINGS, 0, 0); p += 9;
-      auto put_setting = [&](uint16_t k, uint32_t v) {
-        p[0] = k >> 8; p[1] = k; uint32_t nv = htonl(v); memcpy(p + 2, &nv, 4); p += 6;
-      };
-      put_setting(S_MAX_FRAME, OUR_MAX_FRAME);
-      put_setting(S_INITIAL_WINDOW, (uint32_t)RECV_WINDOW);
-      put_setting(S_MAX_CONCURRENT, 1024);
-      put_frame_header(p, 4, F_WINUP, 0, 0);
-      uint32_t inc = htonl((uint32_t)(RECV_WINDOW - DEFAULT_WINDOW));
-      memcpy(p + 9, &inc, 4);
-      p += 13;
-      send_raw(out, p - out);
-    }
+    uint8_t hello[kMaxPreamble];  // our SETTINGS + connection window grant
+    send_raw(hello, put_preamble(hello, /*client=*/false));
     while (!closed_.load()) {
       Frame f;
       if (!read_frame(&f)) break;
@@ -372,13 +185,7 @@ class Connection : public std::enable_shared_from_this<Connection> {
       while (!deferred_.empty()) {
         uint32_t id = deferred_.front();
         deferred_.pop_front();
-        StreamState* stp = nullptr;
-        {
-          std::lock_guard<std::mutex> lk(streams_mu_);
-          auto it = streams_.find(id);
-          if (it != streams_.end()) stp = &it->second;
-        }
-        if (stp) dispatch(*stp, (const uint8_t*)stp->data.data(), stp->data.size());
+        dispatch_buffered(id);
       }
       // bound per-connection recv-deficit bookkeeping: entries accumulate one
       // per stream id; safe to drop whenever no stream is open (conn thread
@@ -435,19 +242,12 @@ class Connection : public std::enable_shared_from_this<Connection> {
     switch (type) {
       case F_SETTINGS:
         if (!(flags & FLAG_ACK)) {
-          for (size_t off = 0; off + 6 <= blen; off += 6) {
-            uint16_t k = body[off] << 8 | body[off + 1];
-            uint32_t v;
-            memcpy(&v, body + off + 2, 4);
-            v = ntohl(v);
-            if (k == S_MAX_FRAME) peer_max_frame_ = v;
-            else if (k == S_INITIAL_WINDOW) {
-              int64_t delta = (int64_t)v - peer_initial_window_;
-              peer_initial_window_ = v;
-              std::lock_guard<std::mutex> lk(win_mu_);
-              for (auto& kv : stream_send_windows_) kv.second += delta;
-              win_cv_.notify_all();
-            }
+          {
+            std::lock_guard<std::mutex> lk(win_mu_);
+            int64_t delta =
+                apply_settings(body, blen, &peer_max_frame_, &peer_initial_window_);
+            for (auto& kv : stream_send_windows_) kv.second += delta;
+            win_cv_.notify_all();
           }
           uint8_t ack[9];
           put_frame_header(ack, 0, F_SETTINGS, FLAG_ACK, 0);
@@ -457,16 +257,13 @@ class Connection : public std::enable_shared_from_this<Connection> {
       case F_PING:
         if (!(flags & FLAG_ACK) && blen == 8) {
           uint8_t p[17];
-          put_frame_header(p, 8, F_PING, FLAG_ACK, 0);
-          memcpy(p + 9, body, 8);
+          put_ping_ack(p, body);
           send_raw(p, 17);
         }
         break;
       case F_WINUP: {
-        if (blen != 4) break;
         uint32_t inc;
-        memcpy(&inc, body, 4);
-        inc = ntohl(inc) & 0x7fffffff;
+        if (!window_increment(f, &inc)) break;
         std::lock_guard<std::mutex> lk(win_mu_);
         if (sid == 0) conn_send_window_ += inc;
         else stream_window_ref(sid) += inc;
@@ -481,13 +278,14 @@ class Connection : public std::enable_shared_from_this<Connection> {
         }
         auto& st = *stp;
         st.id = sid;
-        size_t off = 0, pad = 0;
-        // an empty padded frame has no pad-length byte to read
-        if (flags & FLAG_PADDED) { pad = blen ? body[0] : 0; off = 1; }
-        if (flags & FLAG_PRIORITY) off += 5;
-        if (off > blen || pad > blen - off) { streams_.erase(sid); break; }
-        const uint8_t* block = body + off;
-        size_t block_len = blen - off - pad;
+        const uint8_t* block;
+        size_t block_len;
+        if (!strip_padding(f, /*priority=*/true, &block, &block_len)) {
+          std::lock_guard<std::mutex> lk(streams_mu_);
+          auto it = streams_.find(sid);
+          if (it != streams_.end()) drop_stream(it);
+          break;
+        }
         st.end_stream = st.end_stream || (flags & FLAG_END_STREAM);
         if (flags & FLAG_END_HEADERS) {
           // the view is done with once decoded; dispatch may pump
@@ -501,11 +299,9 @@ class Connection : public std::enable_shared_from_this<Connection> {
         break;
       }
       case F_CONT: {
-        std::unique_lock<std::mutex> lk(streams_mu_);
-        auto it = streams_.find(cont_sid_);
-        if (it == streams_.end()) break;
-        auto& st = it->second;
-        lk.unlock();
+        StreamState* stp = find_stream(cont_sid_);
+        if (!stp) break;
+        auto& st = *stp;
         st.header_accum.append((const char*)body, blen);
         if (flags & FLAG_END_HEADERS) {
           st.end_headers = true;
@@ -518,16 +314,12 @@ class Connection : public std::enable_shared_from_this<Connection> {
         break;
       }
       case F_DATA: {
-        std::unique_lock<std::mutex> lk(streams_mu_);
-        auto it = streams_.find(sid);
-        if (it == streams_.end()) break;
-        auto& st = it->second;
-        lk.unlock();
-        size_t off = 0, pad = 0;
-        if (flags & FLAG_PADDED) { pad = blen ? body[0] : 0; off = 1; }
-        if (off > blen || pad > blen - off) break;
-        const uint8_t* chunk = body + off;
-        size_t chunk_len = blen - off - pad;
+        StreamState* stp = find_stream(sid);
+        if (!stp) break;
+        auto& st = *stp;
+        const uint8_t* chunk;
+        size_t chunk_len;
+        if (!strip_padding(f, /*priority=*/false, &chunk, &chunk_len)) break;
         if (blen) replenish(sid, blen, flags & FLAG_END_STREAM);
         bool end = flags & FLAG_END_STREAM;
         if (end && !defer && st.data.empty()) {
@@ -558,12 +350,7 @@ class Connection : public std::enable_shared_from_this<Connection> {
         auto it = streams_.find(sid);
         if (it != streams_.end()) {
           cancel_ctx(it->second);
-          if (Py_IsInitialized()) {
-            py::gil_scoped_acquire gil;
-            streams_.erase(it);
-          } else {
-            streams_.erase(it);
-          }
+          drop_stream(it);
         }
         break;
       }
@@ -588,13 +375,11 @@ class Connection : public std::enable_shared_from_this<Connection> {
   void replenish(uint32_t sid, size_t consumed, bool stream_done) {
     conn_recv_deficit_ += consumed;
     stream_recv_deficit_[sid] += consumed;
-    std::string upd;
+    uint8_t upd[2 * 13];
+    size_t upd_len = 0;
     auto add = [&](uint32_t id, uint32_t inc) {
-      uint8_t f[13];
-      put_frame_header(f, 4, F_WINUP, 0, id);
-      uint32_t v = htonl(inc);
-      memcpy(f + 9, &v, 4);
-      upd.append((const char*)f, 13);
+      put_window_update(upd + upd_len, id, inc);
+      upd_len += 13;
     };
     if (conn_recv_deficit_ >= RECV_WINDOW / 2) {
       add(0, (uint32_t)conn_recv_deficit_);
@@ -604,7 +389,7 @@ class Connection : public std::enable_shared_from_this<Connection> {
       add(sid, (uint32_t)stream_recv_deficit_[sid]);
       stream_recv_deficit_[sid] = 0;
     }
-    if (!upd.empty()) send_raw(upd.data(), upd.size());
+    if (upd_len) send_raw(upd, upd_len);
   }
 
   int64_t& stream_window_ref(uint32_t sid) {
@@ -628,9 +413,8 @@ class Connection : public std::enable_shared_from_this<Connection> {
       int64_t avail;
       {
         std::lock_guard<std::mutex> lk(win_mu_);
-        avail = std::min(conn_send_window_, stream_window_ref(sid));
+        avail = send_budget(conn_send_window_, stream_window_ref(sid), peer_max_frame_);
       }
-      if ((int64_t)peer_max_frame_ < avail) avail = peer_max_frame_;
       if (avail <= 0) {
         if (closed_.load()) return false;
         if (pump) {
@@ -668,10 +452,13 @@ class Connection : public std::enable_shared_from_this<Connection> {
     send_iov(iov, 2);
   }
 
+  void send_trailers(uint32_t sid, const uint8_t* block, size_t n) {
+    send_headers_frame(sid, block, n, FLAG_END_HEADERS | FLAG_END_STREAM);
+  }
+
   void send_error(uint32_t sid, int code, const std::string& msg) {
     std::string block = error_trailer_block(code, msg);
-    send_headers_frame(sid, (const uint8_t*)block.data(), block.size(),
-                       FLAG_END_HEADERS | FLAG_END_STREAM);
+    send_trailers(sid, (const uint8_t*)block.data(), block.size());
   }
 
   void send_unary_response(uint32_t sid, const uint8_t* msg, size_t msg_len) {
@@ -679,9 +466,8 @@ class Connection : public std::enable_shared_from_this<Connection> {
     bool fits;
     {
       std::lock_guard<std::mutex> lk(win_mu_);
-      fits = (int64_t)payload_len <= conn_send_window_ &&
-             (int64_t)payload_len <= stream_window_ref(sid) &&
-             payload_len <= peer_max_frame_;
+      fits = (int64_t)payload_len <=
+             send_budget(conn_send_window_, stream_window_ref(sid), peer_max_frame_);
     }
     if (fits) {
       // one write: headers + data + trailers, the message sent in place
@@ -707,37 +493,43 @@ class Connection : public std::enable_shared_from_this<Connection> {
     } else {
       send_headers_frame(sid, kRespHdrBlock, sizeof(kRespHdrBlock), FLAG_END_HEADERS);
       send_message(sid, msg, msg_len, /*pump=*/true);
-      send_headers_frame(sid, kOkTrailerBlock, sizeof(kOkTrailerBlock),
-                         FLAG_END_HEADERS | FLAG_END_STREAM);
+      send_trailers(sid, kOkTrailerBlock, sizeof(kOkTrailerBlock));
     }
   }
 
   // ---- dispatch ----
-  void queue_dispatch(uint32_t sid, bool defer) {
-    if (defer) deferred_.push_back(sid);
-    else {
-      StreamState* stp = nullptr;
-      {
-        std::lock_guard<std::mutex> lk(streams_mu_);
-        auto it = streams_.find(sid);
-        if (it != streams_.end()) stp = &it->second;
-      }
-      if (stp) dispatch(*stp, (const uint8_t*)stp->data.data(), stp->data.size());
-    }
+  using StreamMap = std::unordered_map<uint32_t, StreamState>;
+
+  // the entry stays put until it is erased (unordered_map never moves nodes)
+  StreamState* find_stream(uint32_t sid) {
+    std::lock_guard<std::mutex> lk(streams_mu_);
+    auto it = streams_.find(sid);
+    return it == streams_.end() ? nullptr : &it->second;
   }
 
-  // view of the first gRPC message in `body`; empty when incomplete
-  static void first_grpc_message(const uint8_t* body, size_t n,
-                                 const uint8_t** msg, size_t* msg_len) {
-    *msg = body;
-    *msg_len = 0;
-    if (n < 5) return;
-    uint32_t len;
-    memcpy(&len, body + 1, 4);
-    len = ntohl(len);
-    if (5 + (size_t)len > n) return;
-    *msg = body + 5;
-    *msg_len = len;
+  // Erase one stream; the caller holds streams_mu_. The GIL must be held to
+  // drop py objects, and with the interpreter gone the reference is leaked
+  // rather than touched.
+  void drop_stream(StreamMap::iterator it) {
+    py::object& ctx = it->second.ctx;
+    if (ctx && Py_IsInitialized()) {
+      py::gil_scoped_acquire gil;
+      ctx = py::object();
+    } else {
+      ctx.release();
+    }
+    streams_.erase(it);
+  }
+
+  void queue_dispatch(uint32_t sid, bool defer) {
+    if (defer) deferred_.push_back(sid);
+    else dispatch_buffered(sid);
+  }
+
+  // dispatch a stream whose body was accumulated in st.data
+  void dispatch_buffered(uint32_t sid) {
+    if (StreamState* st = find_stream(sid))
+      dispatch(*st, (const uint8_t*)st->data.data(), st->data.size());
   }
 
   void cancel_ctx(StreamState& st) {
@@ -778,62 +570,43 @@ class Connection : public std::enable_shared_from_this<Connection> {
                         std::string((const char*)req, req_len)};
         st.ctx = pack->ctx;
       }
-      // the thread must keep the Connection alive: a raw `this` would dangle
-      // once the client disconnects and the server prunes the connection
-      std::shared_ptr<Connection> self = shared_from_this();
-      core_->live_threads.fetch_add(1);
-      auto core = core_;
-      std::thread([self, pack, sid, core]() {
-        try {
-          self->run_streaming(pack->fn, pack->ctx, pack->request, sid);
-        } catch (abi::__forced_unwind&) {
-          core->live_threads.fetch_sub(1);
-          throw;  // pthread_exit (interpreter finalization)
-        } catch (...) {
-          self->close_now();
-        }
-        if (Py_IsInitialized()) {
-          py::gil_scoped_acquire gil;
-          delete pack;
-        }
-        core->live_threads.fetch_sub(1);
-      }).detach();
+      Connection* self = this;  // kept alive by the launcher's shared_ptr
+      launch_counted(
+          shared_from_this(),
+          [self, pack, sid]() {
+            self->run_streaming(pack->fn, pack->ctx, pack->request, sid);
+          },
+          [pack]() {
+            if (Py_IsInitialized()) {
+              py::gil_scoped_acquire gil;
+              delete pack;
+            }
+          });
       return;
     }
     // unary: inline on the connection thread. The response is copied once
     // into a buffer this connection keeps, so the handler's result can be
     // dropped under the GIL already held and then sent without it.
     std::string& response = resp_buf_;
-    int err_code = -1;
-    std::string err_msg;
+    Status err;
     {
       py::gil_scoped_acquire gil;
       try {
         py::object ctx = core_->context_factory();
         st.ctx = ctx;
         py::object result = it->second.fn(py::bytes((const char*)req, req_len), ctx);
-        char* rb;
-        Py_ssize_t rn;
-        if (PyBytes_AsStringAndSize(result.ptr(), &rb, &rn) == 0) {
-          response.assign(rb, rn);
-        } else {
-          PyErr_Clear();
-          err_code = 13;
-          err_msg = "handler returned non-bytes";
-        }
+        err = take_bytes(result, &response, "handler returned non-bytes");
       } catch (py::error_already_set& e) {
-        auto r = introspect_error(e);
-        err_code = r.first;
-        err_msg = r.second;
+        err = introspect_error(e);
       }
     }
-    if (err_code >= 0) send_error(sid, err_code, err_msg);
+    if (err.failed) send_error(sid, err.code, err.message);
     else send_unary_response(sid, (const uint8_t*)response.data(), response.size());
     cap_retained(response);
     erase_stream(sid);
   }
 
-  std::pair<int, std::string> introspect_error(py::error_already_set& e) {
+  Status introspect_error(py::error_already_set& e) {
     // core_->error_introspect(exc_value) -> (code, message); GIL held
     try {
       py::object val = e.value();
@@ -852,60 +625,31 @@ class Connection : public std::enable_shared_from_this<Connection> {
       ctx = ctx_ref;
     }
     send_headers_frame(sid, kRespHdrBlock, sizeof(kRespHdrBlock), FLAG_END_HEADERS);
-    bool ok = true;
-    int err_code = -1;
-    std::string err_msg;
+    Status err;
     py::object iter;
     {
       py::gil_scoped_acquire gil;
       try {
         iter = py::iter(fn(py::bytes(request), ctx));
       } catch (py::error_already_set& e) {
-        auto r = introspect_error(e);
-        err_code = r.first;
-        err_msg = r.second;
-        ok = false;
+        err = introspect_error(e);
       }
     }
-    while (ok && !closed_.load()) {
+    while (!err.failed && !closed_.load()) {
       std::string item;
       bool done = false;
       {
         py::gil_scoped_acquire gil;
         try {
-          py::handle nxt = PyIter_Next(iter.ptr());
-          if (!nxt) {
-            if (PyErr_Occurred()) {
-              py::error_already_set e;
-              auto r = introspect_error(e);
-              err_code = r.first;
-              err_msg = r.second;
-              ok = false;
-            } else {
-              done = true;
-            }
-          } else {
-            py::object obj = py::reinterpret_steal<py::object>(nxt);
-            char* rb;
-            Py_ssize_t rn;
-            if (PyBytes_AsStringAndSize(obj.ptr(), &rb, &rn) == 0)
-              item.assign(rb, rn);
-            else {
-              PyErr_Clear();
-              err_code = 13;
-              err_msg = "stream yielded non-bytes";
-              ok = false;
-            }
-          }
+          py::object obj = py::reinterpret_steal<py::object>(PyIter_Next(iter.ptr()));
+          if (obj) err = take_bytes(obj, &item, "stream yielded non-bytes");
+          else if (PyErr_Occurred()) throw py::error_already_set();
+          else done = true;
         } catch (py::error_already_set& e) {
-          auto r = introspect_error(e);
-          err_code = r.first;
-          err_msg = r.second;
-          ok = false;
+          err = introspect_error(e);
         }
       }
-      if (done) break;
-      if (!ok) break;
+      if (done || err.failed) break;
       if (!send_message(sid, (const uint8_t*)item.data(), item.size(), /*pump=*/false))
         break;
     }
@@ -916,15 +660,13 @@ class Connection : public std::enable_shared_from_this<Connection> {
       ctx = py::object();
     }
     if (closed_.load()) { erase_stream(sid); return; }
-    if (err_code >= 0) {
+    if (err.failed) {
       // response HEADERS already went out at the top: emit TRAILERS without
       // pseudo-headers (a second :status is a protocol error to grpc-go)
-      std::string block = status_trailer_fields(err_code, err_msg);
-      send_headers_frame(sid, (const uint8_t*)block.data(), block.size(),
-                         FLAG_END_HEADERS | FLAG_END_STREAM);
+      std::string block = status_trailer_fields(err.code, err.message);
+      send_trailers(sid, (const uint8_t*)block.data(), block.size());
     } else {
-      send_headers_frame(sid, kOkTrailerBlock, sizeof(kOkTrailerBlock),
-                         FLAG_END_HEADERS | FLAG_END_STREAM);
+      send_trailers(sid, kOkTrailerBlock, sizeof(kOkTrailerBlock));
     }
     erase_stream(sid);
   }
@@ -933,24 +675,16 @@ class Connection : public std::enable_shared_from_this<Connection> {
     {
       std::lock_guard<std::mutex> lk(streams_mu_);
       auto it = streams_.find(sid);
-      if (it != streams_.end()) {
-        if (it->second.ctx && !it->second.ctx.is_none() && Py_IsInitialized()) {
-          py::gil_scoped_acquire gil;
-          it->second.ctx = py::object();
-          streams_.erase(it);
-        } else {
-          streams_.erase(it);
-        }
-      }
+      if (it != streams_.end()) drop_stream(it);
     }
     std::lock_guard<std::mutex> lk(win_mu_);
     stream_send_windows_.erase(sid);
   }
 
   bool expect_preface() {
-    if (!fill(24)) return false;
-    bool ok = memcmp(buf_.head(), "PRI * HTTP/2.0\r\n\r\nSM\r\n\r\n", 24) == 0;
-    buf_.consume(24);
+    if (!fill(kPrefaceLen)) return false;
+    bool ok = memcmp(buf_.head(), kPreface, kPrefaceLen) == 0;
+    buf_.consume(kPrefaceLen);
     return ok;
   }
 
@@ -958,10 +692,9 @@ class Connection : public std::enable_shared_from_this<Connection> {
     closed_.store(true);
     {
       std::lock_guard<std::mutex> lk(streams_mu_);
-      for (auto& kv : streams_) cancel_ctx(kv.second);
-      if (Py_IsInitialized()) {
-        py::gil_scoped_acquire gil;
-        streams_.clear();  // drops py objects safely
+      while (!streams_.empty()) {
+        cancel_ctx(streams_.begin()->second);
+        drop_stream(streams_.begin());
       }
     }
     {
@@ -1009,11 +742,8 @@ class ServerCore {
     ::unlink(path.c_str());
     listen_fd_ = ::socket(AF_UNIX, SOCK_STREAM, 0);
     if (listen_fd_ < 0) throw std::runtime_error("socket() failed");
-    sockaddr_un addr{};
-    addr.sun_family = AF_UNIX;
-    if (path.size() >= sizeof(addr.sun_path))
-      throw std::runtime_error("socket path too long");
-    strcpy(addr.sun_path, path.c_str());
+    sockaddr_un addr;
+    if (!unix_addr(path, &addr)) throw std::runtime_error("socket path too long");
     if (::bind(listen_fd_, (sockaddr*)&addr, sizeof(addr)) != 0)
       throw std::runtime_error("bind() failed: " + path);
     if (::listen(listen_fd_, 128) != 0) throw std::runtime_error("listen() failed");
@@ -1085,21 +815,8 @@ class ServerCore {
               conns_.end());
         }
       }
-      core_->live_threads.fetch_add(1);
-      auto core = core_;
-      std::thread([conn, core]() {
-        try {
-          conn->run();
-        } catch (abi::__forced_unwind&) {
-          core->live_threads.fetch_sub(1);
-          throw;  // pthread_exit (interpreter finalization)
-        } catch (...) {
-          // a stray exception in a detached thread would std::terminate the
-          // whole process; drop the connection instead
-          conn->close_now();
-        }
-        core->live_threads.fetch_sub(1);
-      }).detach();
+      Connection* c = conn.get();
+      Connection::launch_counted(conn, [c]() { c->run(); }, []() {});
     }
   }
 
@@ -1128,13 +845,11 @@ class ClientCore {
     close_fd();
     fd_ = ::socket(AF_UNIX, SOCK_STREAM, 0);
     if (fd_ < 0) throw std::runtime_error("socket() failed");
-    sockaddr_un addr{};
-    addr.sun_family = AF_UNIX;
-    if (path_.size() >= sizeof(addr.sun_path)) {
+    sockaddr_un addr;
+    if (!unix_addr(path_, &addr)) {
       close_fd();
       throw std::runtime_error("socket path too long");
     }
-    strcpy(addr.sun_path, path_.c_str());
     if (::connect(fd_, (sockaddr*)&addr, sizeof(addr)) != 0) {
       close_fd();
       throw std::runtime_error("connect failed: " + path_);
@@ -1146,22 +861,8 @@ class ClientCore {
     peer_initial_window_ = DEFAULT_WINDOW;
     conn_send_window_ = DEFAULT_WINDOW;
     conn_recv_deficit_ = 0;
-    // preface + SETTINGS + window grant
-    std::string out((const char*)"PRI * HTTP/2.0\r\n\r\nSM\r\n\r\n", 24);
-    uint8_t f[9 + 12 + 13];
-    uint8_t* p = f;
-    put_frame_header(p, 12, F_SETTINGS, 0, 0); p += 9;
-    auto put_setting = [&](uint16_t k, uint32_t v) {
-      p[0] = k >> 8; p[1] = k; uint32_t nv = htonl(v); memcpy(p + 2, &nv, 4); p += 6;
-    };
-    put_setting(S_MAX_FRAME, OUR_MAX_FRAME);
-    put_setting(S_INITIAL_WINDOW, (uint32_t)RECV_WINDOW);
-    put_frame_header(p, 4, F_WINUP, 0, 0);
-    uint32_t inc = htonl((uint32_t)(RECV_WINDOW - DEFAULT_WINDOW));
-    memcpy(p + 9, &inc, 4);
-    p += 13;
-    out.append((const char*)f, p - f);
-    write_all(out.data(), out.size());
+    uint8_t hello[kMaxPreamble];  // preface + SETTINGS + window grant
+    write_all(hello, put_preamble(hello, /*client=*/true));
   }
 
   bool connected() const { return fd_ >= 0; }
@@ -1246,47 +947,30 @@ class ClientCore {
 
   // conn-level frames; returns true if consumed
   bool handle_conn_frame(const Frame& f, int64_t* active_stream_window) {
-    const uint8_t type = f.type, flags = f.flags;
-    const uint32_t sid = f.sid;
-    const uint8_t* body = f.body;
-    const size_t blen = f.len;
-    if (type == F_SETTINGS) {
-      if (!(flags & FLAG_ACK)) {
-        for (size_t off = 0; off + 6 <= blen; off += 6) {
-          uint16_t k = body[off] << 8 | body[off + 1];
-          uint32_t v;
-          memcpy(&v, body + off + 2, 4);
-          v = ntohl(v);
-          if (k == S_MAX_FRAME) peer_max_frame_ = v;
-          else if (k == S_INITIAL_WINDOW) {
-            int64_t delta = (int64_t)v - peer_initial_window_;
-            peer_initial_window_ = v;
-            *active_stream_window += delta;  // RFC 7540 §6.9.2
-          }
-        }
+    if (f.type == F_SETTINGS) {
+      if (!(f.flags & FLAG_ACK)) {
+        *active_stream_window +=
+            apply_settings(f.body, f.len, &peer_max_frame_, &peer_initial_window_);
         uint8_t ack[9];
         put_frame_header(ack, 0, F_SETTINGS, FLAG_ACK, 0);
         write_all(ack, 9);
       }
       return true;
     }
-    if (type == F_PING) {
-      if (!(flags & FLAG_ACK) && blen == 8) {
+    if (f.type == F_PING) {
+      if (!(f.flags & FLAG_ACK) && f.len == 8) {
         uint8_t p[17];
-        put_frame_header(p, 8, F_PING, FLAG_ACK, 0);
-        memcpy(p + 9, body, 8);
+        put_ping_ack(p, f.body);
         write_all(p, 17);
       }
       return true;
     }
-    if (type == F_WINUP && sid == 0) {
-      if (blen != 4) return true;
+    if (f.type == F_WINUP && f.sid == 0) {
       uint32_t inc;
-      memcpy(&inc, body, 4);
-      conn_send_window_ += ntohl(inc) & 0x7fffffff;
+      if (window_increment(f, &inc)) conn_send_window_ += inc;
       return true;
     }
-    if (type == F_GOAWAY) throw std::runtime_error("server sent GOAWAY");
+    if (f.type == F_GOAWAY) throw std::runtime_error("server sent GOAWAY");
     return false;
   }
 
@@ -1308,8 +992,7 @@ class ClientCore {
     bool headers_sent = false;
     size_t off = 0, total = 5 + message_len;
     while (true) {
-      int64_t avail = std::min(conn_send_window_, stream_window);
-      if ((int64_t)peer_max_frame_ < avail) avail = peer_max_frame_;
+      int64_t avail = send_budget(conn_send_window_, stream_window, peer_max_frame_);
       if (avail <= 0) {
         if (!headers_sent) {
           struct iovec hv[2] = {{hhdr, 9}, {(void*)header_block, header_len}};
@@ -1319,12 +1002,9 @@ class ClientCore {
         Frame f;
         read_frame(&f);
         if (!handle_conn_frame(f, &stream_window)) {
+          uint32_t inc;
           if (f.type == F_WINUP && f.sid == sid) {
-            if (f.len == 4) {
-              uint32_t inc;
-              memcpy(&inc, f.body, 4);
-              stream_window += ntohl(inc) & 0x7fffffff;
-            }
+            if (window_increment(f, &inc)) stream_window += inc;
           } else if (f.type == F_RST) {
             throw std::runtime_error("stream reset during send");
           }
@@ -1361,15 +1041,13 @@ class ClientCore {
       if (handle_conn_frame(f, &stream_window)) continue;
       const uint8_t type = f.type, flags = f.flags;
       const uint8_t* body = f.body;
-      const size_t blen = f.len;
+      size_t blen = f.len;
       if (f.sid != sid) continue;
       if (type == F_HEADERS || type == F_CONT) {
-        size_t hoff = 0, pad = 0;
-        if (type == F_HEADERS && (flags & FLAG_PADDED)) { pad = blen ? body[0] : 0; hoff = 1; }
-        if (type == F_HEADERS && (flags & FLAG_PRIORITY)) hoff += 5;
-        if (hoff > blen || pad > blen - hoff)
+        // a CONTINUATION carries neither padding nor PRIORITY fields
+        if (type == F_HEADERS && !strip_padding(f, /*priority=*/true, &body, &blen))
           throw std::runtime_error("bad hpack from server");
-        if (!decoder_.decode(body + hoff, blen - hoff - pad, &headers))
+        if (!decoder_.decode(body, blen, &headers))
           throw std::runtime_error("bad hpack from server");
         if (flags & FLAG_END_STREAM) {
           int st = 0;
@@ -1378,28 +1056,10 @@ class ClientCore {
             if (h.first == "grpc-status") st = atoi(h.second.c_str());
             else if (h.first == "grpc-message") msg = h.second;
           }
-          // grpc-message is percent-encoded; decode minimally
-          std::string dec;
-          for (size_t i = 0; i < msg.size(); ++i) {
-            if (msg[i] == '%' && i + 2 < msg.size()) {
-              dec.push_back((char)strtol(msg.substr(i + 1, 2).c_str(), nullptr, 16));
-              i += 2;
-            } else dec.push_back(msg[i]);
-          }
-          // first grpc message of rdata, as a view
-          *data = (const uint8_t*)rdata.data();
-          *data_len = 0;
-          if (rdata.size() >= 5) {
-            uint32_t len;
-            memcpy(&len, rdata.data() + 1, 4);
-            len = ntohl(len);
-            if (5 + (size_t)len <= rdata.size()) {
-              *data = (const uint8_t*)rdata.data() + 5;
-              *data_len = len;
-            }
-          }
+          // `*data` is a view into rdata
+          first_grpc_message((const uint8_t*)rdata.data(), rdata.size(), data, data_len);
           *status = st;
-          *grpc_message = dec;
+          *grpc_message = percent_decode(msg);
           return;
         }
       } else if (type == F_DATA) {
@@ -1407,13 +1067,10 @@ class ClientCore {
         if (blen) {
           conn_recv_deficit_ += blen;
           if (conn_recv_deficit_ >= RECV_WINDOW / 2) {
-            uint8_t f2[26];
-            put_frame_header(f2, 4, F_WINUP, 0, 0);
-            uint32_t v = htonl((uint32_t)conn_recv_deficit_);
-            memcpy(f2 + 9, &v, 4);
-            put_frame_header(f2 + 13, 4, F_WINUP, 0, sid);
-            memcpy(f2 + 22, &v, 4);
-            write_all(f2, 26);
+            uint8_t f2[2 * 13];
+            put_window_update(f2, 0, (uint32_t)conn_recv_deficit_);
+            put_window_update(f2 + 13, sid, (uint32_t)conn_recv_deficit_);
+            write_all(f2, sizeof(f2));
             conn_recv_deficit_ = 0;
           }
         }
@@ -1436,6 +1093,15 @@ class ClientCore {
   int64_t conn_send_window_ = DEFAULT_WINDOW;
   int64_t conn_recv_deficit_ = 0;
 };
+
+void fatal_backtrace(int sig) {
+  void* frames[64];
+  int n = backtrace(frames, 64);
+  fprintf(stderr, "[etransport] FATAL signal %d, backtrace:\n", sig);
+  backtrace_symbols_fd(frames, n, 2);
+  signal(sig, SIG_DFL);
+  raise(sig);
+}
 
 }  // namespace
 
@@ -1461,22 +1127,8 @@ PYBIND11_MODULE(_etransport, m) {
   trie_init();
   if (const char* dbg = getenv("EGPU_ETRANSPORT_DEBUG"); dbg && dbg[0] == '1') {
     // crash diagnostics for pool boxes without a debugger
-    signal(SIGSEGV, [](int sig) {
-      void* frames[64];
-      int n = backtrace(frames, 64);
-      fprintf(stderr, "[etransport] FATAL signal %d, backtrace:\n", sig);
-      backtrace_symbols_fd(frames, n, 2);
-      signal(sig, SIG_DFL);
-      raise(sig);
-    });
-    signal(SIGABRT, [](int sig) {
-      void* frames[64];
-      int n = backtrace(frames, 64);
-      fprintf(stderr, "[etransport] FATAL signal %d, backtrace:\n", sig);
-      backtrace_symbols_fd(frames, n, 2);
-      signal(sig, SIG_DFL);
-      raise(sig);
-    });
+    signal(SIGSEGV, fatal_backtrace);
+    signal(SIGABRT, fatal_backtrace);
   }
   m.doc() = "C++ data plane for the egrpc server";
   py::class_<HpackTester>(m, "HpackTester")

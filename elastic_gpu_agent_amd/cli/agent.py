@@ -48,6 +48,11 @@ def main(argv=None) -> int:
     parser.add_argument("--gpu-selftest-timeout", type=float, default=10.0,
                         help="time limit of one self-test probe; a probe that "
                              "exceeds it makes its GPU Unhealthy")
+    parser.add_argument("--recordFormat", choices=["runs", "list"], default="runs",
+                        help="how the state DB holds a large consecutive device "
+                             "set: as ID runs, or as the literal list that "
+                             "builds before the runs form read (use list "
+                             "before rolling back to such a build)")
     # path overrides (defaults match the DaemonSet mounts; overridable for
     # local runs and tests)
     parser.add_argument("--plugin-dir", default=None, help="kubelet device-plugins dir")
@@ -101,6 +106,7 @@ def main(argv=None) -> int:
         workers=args.workers,
         selftest_seconds=args.gpu_selftest_seconds,
         selftest_timeout=args.gpu_selftest_timeout,
+        record_format=args.recordFormat,
     )
     manager = GPUManager(opts)
     manager.run()

@@ -52,7 +52,7 @@ def cmd_pods(args) -> int:
             {
                 "pod": pi.key(),
                 "containers": {
-                    c: {"hash": d.hash, "resource": d.resource_name, "units": len(d.list)}
+                    c: {"hash": d.hash, "resource": d.resource_name, "units": d.n_ids}
                     for c, d in pi.container_device_map.items()
                 },
             }

@@ -43,6 +43,10 @@ class ManagerOptions:
     # the GPUs, 0 = off; and the time limit of one probe child
     selftest_seconds: float = 0.0
     selftest_timeout: float = 10.0
+    # how the store's rows hold a large consecutive device set: "runs"
+    # (ID runs) or "list" (the reference-format record; the way back for a
+    # rollback to a build that cannot read runs)
+    record_format: str = "runs"
 
     def to_json(self) -> str:
         import dataclasses
@@ -69,7 +73,7 @@ class GPUManager:
 
         from .storage import new_storage
 
-        self.storage = storage or new_storage(opts.db_path)
+        self.storage = storage or new_storage(opts.db_path, opts.record_format)
 
         if opts.backend == "fake":
             backend = FakeBackend()

@@ -1,6 +1,7 @@
 """Build + (optionally) run the libFuzzer harness over the native parsers,
 and the stand-alone sanitizer self-tests of the device-set digest, of the
-GPU self-test's host reference and of the transport's HTTP/2 framing core.
+ID-run codec the store uses, of the GPU self-test's host reference and of the
+transport's HTTP/2 framing core.
 
 Usage:
   python -m elastic_gpu_agent_amd.native.build_fuzz             # build only
@@ -8,6 +9,7 @@ Usage:
   python -m elastic_gpu_agent_amd.native.build_fuzz --replay    # in-tree corpus, once
   python -m elastic_gpu_agent_amd.native.build_fuzz --selftest  # ASan+UBSan digest cases
                                                                 # (general, then fixed-stride/radix),
+                                                                # then the ID-run codec,
                                                                 # then selftest_ref.h,
                                                                 # then h2frame.h
 """
@@ -38,10 +40,21 @@ def build(out=None):
     return out
 
 
+# checked-in inputs: findings of past sessions, and the seeds of the ID-run
+# codec (wire bodies for the digest differential, stored runs fragments)
+SEED_DIRS = [
+    os.path.join(REPO, "tests", "fuzz_regressions_corpus"),
+    os.path.join(REPO, "tests", "golden", "fuzz_runs_seeds"),
+]
+
+
 def run(binary, seconds=30, corpus=None):
     corpus = corpus or os.path.join(REPO, "tests", "fuzz_corpus")
     os.makedirs(corpus, exist_ok=True)
-    cmd = [binary, corpus, f"-max_total_time={seconds}", "-max_len=65536",
+    # libFuzzer writes new units to the first directory only; the checked-in
+    # ones are read as seeds
+    cmd = [binary, corpus, *[d for d in SEED_DIRS if os.path.isdir(d)],
+           f"-max_total_time={seconds}", "-max_len=65536",
            "-print_final_stats=1"]
     print("+", " ".join(cmd), flush=True)
     return subprocess.call(cmd)
@@ -49,8 +62,8 @@ def run(binary, seconds=30, corpus=None):
 
 def replay(binary, corpus=None):
     """Run every input of the checked-in corpus through the harness once."""
-    corpus = corpus or os.path.join(REPO, "tests", "fuzz_regressions_corpus")
-    inputs = sorted(os.path.join(corpus, f) for f in os.listdir(corpus))
+    dirs = [corpus] if corpus else [d for d in SEED_DIRS if os.path.isdir(d)]
+    inputs = sorted(os.path.join(d, f) for d in dirs for f in os.listdir(d))
     cmd = [binary, *inputs]
     print("+", binary, f"<{len(inputs)} corpus inputs>", flush=True)
     return subprocess.call(cmd)
@@ -79,6 +92,13 @@ def build_stride_selftest(out=None):
     return build_selftest(out, "digest_stride_selftest.cpp")
 
 
+def build_runs_selftest(out=None):
+    """runs_selftest.cpp: the ID-run codec of wirecore.h (digest_field_runs,
+    expand_runs), built the same way."""
+    out = out or os.path.join(REPO, "bin", "egpu-runs-selftest")
+    return build_selftest(out, "runs_selftest.cpp")
+
+
 def build_ref_selftest(out=None):
     """selftest_ref_selftest.cpp: the host reference of the GPU self-test
     (selftest_ref.h, no GPU code), built the same way."""
@@ -98,6 +118,7 @@ if __name__ == "__main__":
     if "--selftest" in sys.argv:
         rc = subprocess.call([build_selftest()])
         rc = rc or subprocess.call([build_stride_selftest()])
+        rc = rc or subprocess.call([build_runs_selftest()])
         rc = rc or subprocess.call([build_ref_selftest()])
         sys.exit(rc or subprocess.call([build_h2frame_selftest()]))
     binary = build()

@@ -760,6 +760,13 @@ class ServerCore {
   }
 
   void start() {
+    // A stop() from another thread can come between bind and start (a plugin
+    // server stopped while its own thread is still bringing it up). The
+    // accept thread must then not be created: stop() has already done its
+    // join, and a joinable std::thread left in a ServerCore aborts the
+    // process when the object is destroyed.
+    std::lock_guard<std::mutex> stop_lk(stop_mu_);
+    if (stopped_ || accept_thread_.joinable()) return;
     accept_thread_ = std::thread([this]() { accept_loop(); });
   }
 
@@ -793,8 +800,14 @@ class ServerCore {
   }
 
   ~ServerCore() {
-    // stop() must have been called from Python; guard anyway
-    if (listen_fd_ >= 0) ::close(listen_fd_);
+    // stop() must have been called from Python; guard anyway. The accept
+    // thread never takes the GIL, so joining it here is safe.
+    core_->stopping.store(true);
+    if (listen_fd_ >= 0) {
+      ::shutdown(listen_fd_, SHUT_RDWR);
+      ::close(listen_fd_);
+    }
+    if (accept_thread_.joinable()) accept_thread_.join();
   }
 
  private:

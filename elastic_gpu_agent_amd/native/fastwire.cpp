@@ -238,6 +238,79 @@ py::tuple decode_prestart_digest2(py::bytes data) {
                         py::bytes(sc.json.data(), d.json_len));
 }
 
+// PreStart digest v3: as v2, but a large set of consecutive IDs comes back as
+// its runs fragment ([[prefix, width, start, count], ...], is_runs = True)
+// and its literal list is never built: the store keeps the runs, and
+// expand_runs rebuilds the list for the few readers that want it. Sets that
+// do not qualify (wirecore.h, "ID runs") come back exactly as from v2.
+py::tuple decode_prestart_digest3(py::bytes data) {
+  char* buf;
+  Py_ssize_t len;
+  PyBytes_AsStringAndSize(data.ptr(), &buf, &len);
+  DigestScratch& sc = wirecore::digest_scratch();
+  ScratchGuard guard(sc);
+  DigestOut d;
+  bool is_runs = false;
+  {
+    py::gil_scoped_release rel;
+    d = wirecore::digest_field_runs(sc, (const uint8_t*)buf, (size_t)len, 1, sha256_evp,
+                                    &is_runs);
+  }
+  return py::make_tuple(py::str(d.hex, 8), (long long)d.count,
+                        py::bytes(sc.json.data(), d.json_len), is_runs);
+}
+
+// The runs fragment of an already sorted list of IDs (a Device built from
+// Python strings), or None when the set does not qualify.
+py::object ids_to_runs(py::list ids) {
+  const size_t n = ids.size();
+  if (n < wirecore::kRunsMinIds) return py::none();
+  std::vector<Span> spans;
+  spans.reserve(n);
+  for (size_t i = 0; i < n; ++i) {
+    Py_ssize_t sz;
+    // the UTF-8 form is cached in the str object, which the list keeps alive
+    const char* s = PyUnicode_AsUTF8AndSize(PyList_GET_ITEM(ids.ptr(), i), &sz);
+    if (!s) throw py::error_already_set();
+    spans.emplace_back((const uint8_t*)s, (size_t)sz);
+  }
+  std::string out;
+  bool ok;
+  {
+    py::gil_scoped_release rel;
+    wirecore::RunBuilder rb;
+    rb.reset(n / wirecore::kRunsPerIds);
+    for (auto& s : spans) rb.add(s.first, s.second);
+    ok = rb.qualifies();
+    if (ok) rb.to_json(out);
+  }
+  if (!ok) return py::none();
+  return py::bytes(out);
+}
+
+// runs fragment + the record's ID count -> the literal list fragment, byte
+// for byte what decode_prestart_digest2 returns for that set
+py::bytes expand_runs(py::bytes frag, long long count) {
+  char* buf;
+  Py_ssize_t len;
+  PyBytes_AsStringAndSize(frag.ptr(), &buf, &len);
+  if (count < 0) throw std::runtime_error("runs: negative count");
+  wirecore::RunsPlan plan;
+  {
+    py::gil_scoped_release rel;
+    plan = wirecore::parse_runs(buf, (size_t)len, (uint64_t)count);
+  }
+  PyObject* out = PyBytes_FromStringAndSize(nullptr, (Py_ssize_t)plan.total);
+  if (!out) throw py::error_already_set();
+  py::bytes result = py::reinterpret_steal<py::bytes>(out);
+  char* dst = PyBytes_AS_STRING(out);
+  {
+    py::gil_scoped_release rel;
+    wirecore::write_runs(plan, dst);
+  }
+  return result;
+}
+
 // ---- podresources List digest --------------------------------------------
 // ListPodResourcesResponse walker: per (pod, container, resource) compute the
 // device-set hash + count straight off the wire. The locator's job is "which
@@ -559,6 +632,9 @@ PYBIND11_MODULE(_fastwire, m) {
   m.def("digest_allocate_request", &digest_allocate_request);
   m.def("decode_prestart_digest", &decode_prestart_digest);
   m.def("decode_prestart_digest2", &decode_prestart_digest2);
+  m.def("decode_prestart_digest3", &decode_prestart_digest3);
+  m.def("ids_to_runs", &ids_to_runs);
+  m.def("expand_runs", &expand_runs);
   m.def("preferred_digest", &preferred_digest);
   m.def("podresources_digest", &podresources_digest);
   m.def("preferred_extract", &preferred_extract);

@@ -8,14 +8,19 @@
 //   1: Huffman string decode
 //   2: protobuf wire walk (wirecore.h field1_spans — the code in _fastwire)
 //   3: AllocateRequest digest (outer field1 → wirecore.h digest_field per
-//      container: the fused walk/check/join/hash helper behind _fastwire)
-//   4: minijson parse (OCI config/state parsing in egpu-hook)
+//      container: the fused walk/check/join/hash helper behind _fastwire),
+//      and the same set through digest_field_runs: where it comes back as ID
+//      runs, expanding them must give the literal list fragment
+//   4: minijson parse (OCI config/state parsing in egpu-hook); the same
+//      bytes, read as a 16-bit ID count and a runs fragment, through
+//      wirecore.h expand_runs (what the store reads back)
 //   5: devfilter OCI device-rule extraction + eBPF program build
 //
 // Build + run: python -m elastic_gpu_agent_amd.native.build_fuzz
 //              (clang -fsanitize=fuzzer,address from /opt/rocm's LLVM)
 #include <cstddef>
 #include <cstdint>
+#include <cstdlib>
 #include <string>
 #include <vector>
 
@@ -92,6 +97,20 @@ void fuzz_wire_nested(const uint8_t* data, size_t size) {
         // sorted, byte-wise, shorter prefix first
         if (i && wirecore::span_less(s, sc.spans[i - 1])) __builtin_trap();
       }
+      // runs: same hash and count; expand(compress(set)) is the list fragment
+      const size_t count = d.count;
+      bool is_runs = false;
+      wirecore::DigestOut r =
+          wirecore::digest_field_runs(sc, o.first, o.second, 1, sum_digest, &is_runs);
+      if (hex_no_spans != r.hex || r.count != count) __builtin_trap();
+      if (r.json_len > sc.json.size()) __builtin_trap();
+      if (is_runs) {
+        if (count < wirecore::kRunsMinIds) __builtin_trap();
+        if (wirecore::expand_runs(sc.json.data(), r.json_len, count) != json_no_spans)
+          __builtin_trap();
+      } else if (json_no_spans != std::string(sc.json.data(), r.json_len)) {
+        __builtin_trap();
+      }
     }
   } catch (const std::runtime_error&) {
   }
@@ -105,6 +124,22 @@ void fuzz_minijson(const uint8_t* data, size_t size) {
     (void)v->get("linux").get("resources").get("devices").is_arr();
     (void)v->get("process").get("env").is_arr();
     (void)v->get("pid").as_int(0);
+  }
+}
+
+// arbitrary bytes as a stored runs fragment: parse_runs must refuse or size
+// the expansion exactly; the block is exact-size so ASan sees either end
+void fuzz_runs_expand(const uint8_t* data, size_t size) {
+  if (size < 2) return;
+  const uint64_t count = data[0] | (uint64_t)data[1] << 8;
+  try {
+    wirecore::RunsPlan plan = wirecore::parse_runs((const char*)data + 2, size - 2, count);
+    if (plan.total > wirecore::kScratchCap) __builtin_trap();
+    char* out = (char*)malloc(plan.total);
+    wirecore::write_runs(plan, out);
+    if (out[0] != '[' || out[plan.total - 1] != ']') __builtin_trap();
+    free(out);
+  } catch (const std::runtime_error&) {
   }
 }
 
@@ -134,7 +169,7 @@ extern "C" int LLVMFuzzerTestOneInput(const uint8_t* data, size_t size) {
     case 1: fuzz_huffman(data, size); break;
     case 2: fuzz_wire(data, size); break;
     case 3: fuzz_wire_nested(data, size); break;
-    case 4: fuzz_minijson(data, size); break;
+    case 4: fuzz_minijson(data, size); fuzz_runs_expand(data, size); break;
     case 5: fuzz_devfilter(data, size); break;
   }
   return 0;

@@ -201,6 +201,153 @@ inline bool span_less(const Span& a, const Span& b) {
   return a.second < b.second;
 }
 
+// ---- ID runs ----------------------------------------------------------------
+// The IDs of a resource are "<gpu>-<zero-padded index>", and kubelet hands out
+// mostly consecutive ones, so a large sorted set is a handful of runs. The
+// store keeps such a set as [[prefix, width, start, count], ...] (200 KB of
+// literal list become ~20 bytes); the literal list stays the exchange format
+// and expand_runs rebuilds it byte for byte.
+//
+// An ID is run-encodable when it ends in a maximal run of 1..18 ASCII digits
+// (so the value fits a uint64) and holds no byte json.dumps would escape
+// ('"', '\\', < 0x20, >= 0x80). Over the sorted set an ID with the prefix and
+// width of its predecessor and value == previous + 1 extends the run; anything
+// else (a duplicate, 9 -> 10, another prefix) starts one. A set is stored as
+// runs only when every ID is run-encodable, it has >= kRunsMinIds IDs and at
+// most count / kRunsPerIds runs: small sets keep their literal bytes and a
+// fragmented set never grows.
+
+constexpr size_t kRunsMinIds = 1024;
+constexpr size_t kRunsPerIds = 8;
+constexpr size_t kRunsMaxWidth = 18;
+
+struct IdRun {
+  size_t prefix_off, prefix_len;  // into RunBuilder::prefixes
+  unsigned width;
+  uint64_t start, count;
+};
+
+// Fed the sorted IDs one by one. The expected successor is kept as text, so
+// an ID that extends the run costs one compare and an ASCII increment. The
+// digest's word-at-a-time loops see "previous ID + 1 in the last digit, no
+// carry" on the words they already hold and only report how many such IDs
+// went by (extend).
+struct RunBuilder {
+  std::vector<IdRun> runs;
+  std::string prefixes;
+  std::string next;  // the ID that would extend the last run
+  bool has_next = false;
+  bool ok = true;    // every ID so far is run-encodable, runs within max_runs
+  size_t n = 0;
+  size_t max_runs = 0;
+
+  void reset(size_t run_cap) {
+    runs.clear();
+    prefixes.clear();
+    has_next = false;
+    ok = true;
+    n = 0;
+    max_runs = run_cap;
+  }
+
+  // `next` += 1 in its last `width` bytes; no successor at 99..9
+  void advance() {
+    const size_t w = runs.back().width;
+    size_t i = next.size();
+    for (size_t k = 0; k < w; ++k) {
+      char& c = next[--i];
+      if (c != '9') {
+        ++c;
+        return;
+      }
+      c = '0';
+    }
+    has_next = false;
+  }
+
+  // the last run grew by k IDs, each its predecessor with the last digit
+  // one higher (so k <= 9 and `next` is the first of them)
+  void extend(size_t k) {
+    if (!k || !ok || !has_next) return;
+    runs.back().count += k;
+    n += k;
+    next[next.size() - 1] = (char)(next[next.size() - 1] + (char)(k - 1));
+    advance();
+  }
+
+  void add(const uint8_t* id, size_t len) {
+    if (!ok) return;
+    ++n;
+    if (has_next && len == next.size() && memcmp(id, next.data(), len) == 0) {
+      ++runs.back().count;
+      advance();
+      return;
+    }
+    size_t w = 0;
+    while (w < len && (unsigned)(id[len - 1 - w] - '0') < 10) ++w;
+    if (w == 0 || w > kRunsMaxWidth || runs.size() >= max_runs) {
+      ok = false;
+      return;
+    }
+    const size_t plen = len - w;
+    for (size_t i = 0; i < plen; ++i) {
+      const uint8_t c = id[i];
+      if (c < 0x20 || c >= 0x80 || c == '"' || c == '\\') {
+        ok = false;
+        return;
+      }
+    }
+    uint64_t v = 0;
+    for (size_t i = plen; i < len; ++i) v = v * 10 + (id[i] - '0');
+    IdRun r;
+    r.prefix_len = plen;
+    r.width = (unsigned)w;
+    r.start = v;
+    r.count = 1;
+    if (!runs.empty() && runs.back().prefix_len == plen &&
+        memcmp(prefixes.data() + runs.back().prefix_off, id, plen) == 0) {
+      r.prefix_off = runs.back().prefix_off;
+    } else {
+      r.prefix_off = prefixes.size();
+      prefixes.append((const char*)id, plen);
+    }
+    runs.push_back(r);
+    next.assign((const char*)id, len);
+    has_next = true;
+    advance();
+  }
+
+  bool qualifies() const {
+    return ok && n >= kRunsMinIds && runs.size() * kRunsPerIds <= n;
+  }
+
+  // compact JSON: [["0-",6,0,18432]]
+  void to_json(std::string& out) const {
+    out.clear();
+    out.push_back('[');
+    char num[24];
+    for (size_t i = 0; i < runs.size(); ++i) {
+      const IdRun& r = runs[i];
+      if (i) out.push_back(',');
+      out.append("[\"");
+      out.append(prefixes, r.prefix_off, r.prefix_len);
+      out.append("\",");
+      const uint64_t f[3] = {r.width, r.start, r.count};
+      for (int k = 0; k < 3; ++k) {
+        char* e = num + sizeof num;
+        uint64_t v = f[k];
+        do {
+          *--e = (char)('0' + v % 10);
+          v /= 10;
+        } while (v);
+        out.append(e, num + sizeof num - e);
+        out.push_back(k < 2 ? ',' : ']');
+      }
+    }
+    out.push_back(']');
+  }
+};
+
 // The strings are used as raw storage: size() is the high-water mark of what
 // was ever needed (so growing zero-fills only new bytes), and each call
 // tracks its own used lengths locally. Bytes past those lengths are stale
@@ -210,12 +357,16 @@ struct DigestScratch {
   std::string json;
   std::vector<Span> spans;
   std::vector<uint64_t> keys;  // radix fallback: n keys + n for the passes
+  RunBuilder runs;             // digest_field_runs only
 
   void trim() {
     if (joined.capacity() > kScratchCap) std::string().swap(joined);
     if (json.capacity() > kScratchCap) std::string().swap(json);
     if (spans.capacity() * sizeof(Span) > kScratchCap) std::vector<Span>().swap(spans);
     if (keys.capacity() * sizeof(uint64_t) > kScratchCap) std::vector<uint64_t>().swap(keys);
+    if (runs.runs.capacity() * sizeof(IdRun) > kScratchCap) std::vector<IdRun>().swap(runs.runs);
+    if (runs.prefixes.capacity() > kScratchCap) std::string().swap(runs.prefixes);
+    if (runs.next.capacity() > kScratchCap) std::string().swap(runs.next);
   }
 };
 
@@ -277,11 +428,12 @@ struct DigestOut {
 struct DigestWriter {
   DigestScratch& s;
   bool want_json;
+  RunBuilder* rb;     // also split the IDs into runs (may be null)
   char *jo, *jo_end;  // joined cursor / end of storage
   char *js, *js_end;  // json cursor / end of storage
 
-  DigestWriter(DigestScratch& sc, size_t in_bytes, bool json)
-      : s(sc), want_json(json) {
+  DigestWriter(DigestScratch& sc, size_t in_bytes, bool json, RunBuilder* runs = nullptr)
+      : s(sc), want_json(json), rb(runs) {
     // the joined bytes never outgrow the input: an entry takes >= 2 wire
     // bytes beyond its payload and <= 1 separator byte joined
     if (s.joined.size() < in_bytes + 1 + kWordSlack) s.joined.resize(in_bytes + 1 + kWordSlack);
@@ -301,6 +453,7 @@ struct DigestWriter {
 
   void restart() {
     jo = &s.joined[0];
+    if (rb) rb->reset(rb->max_runs);
     if (want_json) {
       js = &s.json[0];
       *js++ = '[';
@@ -324,6 +477,7 @@ struct DigestWriter {
     if (!first) *j++ = ':';
     memcpy(j, id.first, n);
     jo = j + n;
+    if (rb) rb->add(id.first, n);
     if (want_json) {
       json_room(6 * n + 4);  // literal + comma + closing bracket
       char* q = js;
@@ -356,7 +510,13 @@ struct DigestWriter {
     const uint8_t* last = nullptr;
     size_t n = 0;
     bool in_order = true;
+    // runs: an entry that is its predecessor with the last digit one higher
+    // is only counted; every other one goes through RunBuilder::add
+    RunBuilder* rbl = rb && rb->ok ? rb : nullptr;
+    size_t matched = 0;
     if (L <= 8) {
+      const int sh = 64 - 8 * (int)L;
+      const uint64_t unit = 1ull << sh;
       const uint64_t mask = ~0ull << (64 - 8 * L);
       // the bytes past the ID must not look like bytes to escape
       const uint64_t pad = ~mask & 0x3030303030303030ull;
@@ -372,6 +532,16 @@ struct DigestWriter {
         if (key < pk) {
           in_order = false;
           break;
+        }
+        if (rbl) {
+          if (key - pk == unit && (unsigned)(((pk >> sh) & 0xFF) - '0') < 9) {
+            ++matched;
+          } else {
+            rbl->extend(matched);
+            matched = 0;
+            rbl->add(pay, L);
+            if (!rbl->ok) rbl = nullptr;
+          }
         }
         pk = key;
         *j = ':';
@@ -415,6 +585,16 @@ struct DigestWriter {
           in_order = false;
           break;
         }
+        if (rbl) {
+          if (kh == ph && kl - pl == 1 && (unsigned)((pl & 0xFF) - '0') < 9) {
+            ++matched;
+          } else {
+            rbl->extend(matched);
+            matched = 0;
+            rbl->add(pay, L);
+            if (!rbl->ok) rbl = nullptr;
+          }
+        }
         ph = kh;
         pl = kl;
         *j = ':';
@@ -443,6 +623,7 @@ struct DigestWriter {
         p += stride;
       }
     }
+    if (rbl) rbl->extend(matched);
     jo = j;
     js = q;
     r.p = p;
@@ -460,12 +641,29 @@ struct DigestWriter {
     char* j = jo;
     char* q = js;
     const uint64_t pad = L == 8 ? 0 : (0x3030303030303030ull >> (8 * L));
+    RunBuilder* rbl = rb && rb->ok ? rb : nullptr;
+    size_t matched = 0;
+    const int sh = 64 - 8 * (int)L;
+    const uint64_t unit = 1ull << sh;
     for (size_t i = 0; i < n; ++i) {
       const uint64_t key = keys[i];
       const uint64_t raw = word_to_be(key);
       if (i) *j++ = ':';
       memcpy(j, &raw, 8);
       j += L;
+      if (rbl) {
+        if (i && key - keys[i - 1] == unit &&
+            (unsigned)(((keys[i - 1] >> sh) & 0xFF) - '0') < 9) {
+          ++matched;
+        } else {
+          uint8_t id[8];
+          memcpy(id, &raw, 8);
+          rbl->extend(matched);
+          matched = 0;
+          rbl->add(id, L);
+          if (!rbl->ok) rbl = nullptr;
+        }
+      }
       if (want_json) {
         if (i) *q++ = ',';
         if (word_needs_escape(key | pad)) {
@@ -482,10 +680,12 @@ struct DigestWriter {
         }
       }
     }
+    if (rbl) rbl->extend(matched);
     jo = j;
     js = q;
   }
 
+  // a null `sha` leaves the hash out (hex stays empty)
   DigestOut finish(size_t count, Sha256Fn sha) {
     DigestOut out;
     out.json_len = 0;
@@ -494,6 +694,9 @@ struct DigestWriter {
       *js++ = ']';
       out.json_len = js - &s.json[0];
     }
+    out.hex[0] = 0;
+    out.count = count;
+    if (!sha) return out;
     unsigned char md[32];
     sha(s.joined.data(), jo - &s.joined[0], md);
     static const char kHex[] = "0123456789abcdef";
@@ -502,7 +705,6 @@ struct DigestWriter {
       out.hex[2 * i + 1] = kHex[md[i] & 15];
     }
     out.hex[8] = 0;
-    out.count = count;
     return out;
   }
 };
@@ -515,10 +717,10 @@ struct DigestWriter {
 // the ScratchGuard.
 inline DigestOut digest_ranges(DigestScratch& s, const Span* ranges, size_t nranges,
                                uint32_t want, bool want_json, bool want_spans,
-                               Sha256Fn sha) {
+                               Sha256Fn sha, RunBuilder* runs = nullptr) {
   size_t in_bytes = 0;
   for (size_t i = 0; i < nranges; ++i) in_bytes += ranges[i].second;
-  DigestWriter w(s, in_bytes, want_json);
+  DigestWriter w(s, in_bytes, want_json, runs);
   bool sorted = true, have_prev = false;
   Span prev{nullptr, 0};
   size_t count = 0;
@@ -623,6 +825,186 @@ inline DigestOut digest_field(DigestScratch& s, const uint8_t* p, size_t len,
                               Sha256Fn sha) {
   Span range{p, len};
   return digest_ranges(s, &range, 1, want, want_json, want_spans, sha);
+}
+
+// digest_field for a caller that stores runs: scratch.json[0, json_len) holds
+// the runs fragment and *is_runs is set when the set qualifies, the literal
+// list fragment otherwise. A set that qualifies never has its literal list
+// built. One that is large enough to try and then does not qualify (an ID
+// that is not run-encodable, too many runs) is walked a second time for the
+// list, without hashing again.
+inline DigestOut digest_field_runs(DigestScratch& s, const uint8_t* p, size_t len,
+                                   uint32_t want, Sha256Fn sha, bool* is_runs) {
+  *is_runs = false;
+  // an entry takes >= 3 wire bytes (tag, length, one digit)
+  if (len < 3 * kRunsMinIds) return digest_field(s, p, len, want, true, false, sha);
+  Span range{p, len};
+  s.runs.reset(len / (3 * kRunsPerIds));
+  DigestOut d = digest_ranges(s, &range, 1, want, false, false, sha, &s.runs);
+  if (s.runs.qualifies() && s.runs.n == d.count) {
+    s.runs.to_json(s.json);
+    d.json_len = s.json.size();
+    *is_runs = true;
+    return d;
+  }
+  DigestOut l = digest_ranges(s, &range, 1, want, true, false, nullptr);
+  d.json_len = l.json_len;
+  return d;
+}
+
+// ---- runs -> literal list ----------------------------------------------------
+// parse_runs checks a runs fragment against the ID count its record states
+// and sizes the expansion; write_runs then fills exactly plan.total bytes.
+// Nothing is allocated for the expansion before every check has passed:
+// counts must sum to expected_count, start + count <= 10^width, width in
+// 1..18, total <= kScratchCap. Prefix spans point into the fragment.
+
+struct RunsPlan {
+  struct Run {
+    const char* prefix;
+    size_t prefix_len;
+    unsigned width;
+    uint64_t start, count;
+  };
+  std::vector<Run> runs;
+  size_t total = 2;  // "[]"
+};
+
+namespace runs_detail {
+
+inline void ws(const char*& p, const char* end) {
+  while (p < end && (*p == ' ' || *p == '\t' || *p == '\n' || *p == '\r')) ++p;
+}
+
+inline void expect(const char*& p, const char* end, char c) {
+  ws(p, end);
+  if (p >= end || *p != c) throw std::runtime_error("runs: malformed fragment");
+  ++p;
+}
+
+// a JSON non-negative integer below 10^18: digits only, no leading zero
+inline uint64_t uint_field(const char*& p, const char* end) {
+  ws(p, end);
+  const char* b = p;
+  uint64_t v = 0;
+  while (p < end && (unsigned)(*p - '0') < 10) {
+    if (p - b >= 18) throw std::runtime_error("runs: number too long");
+    v = v * 10 + (uint64_t)(*p - '0');
+    ++p;
+  }
+  if (p == b || (p - b > 1 && *b == '0'))
+    throw std::runtime_error("runs: not a non-negative integer");
+  if (p < end && (*p == '.' || *p == 'e' || *p == 'E'))
+    throw std::runtime_error("runs: not an integer");
+  return v;
+}
+
+}  // namespace runs_detail
+
+inline RunsPlan parse_runs(const char* frag, size_t len, uint64_t expected_count) {
+  using namespace runs_detail;
+  static const uint64_t kPow10[19] = {
+      1ull, 10ull, 100ull, 1000ull, 10000ull, 100000ull, 1000000ull, 10000000ull,
+      100000000ull, 1000000000ull, 10000000000ull, 100000000000ull, 1000000000000ull,
+      10000000000000ull, 100000000000000ull, 1000000000000000ull, 10000000000000000ull,
+      100000000000000000ull, 1000000000000000000ull};
+  RunsPlan plan;
+  const char* p = frag;
+  const char* const end = frag + len;
+  uint64_t left = expected_count;
+  expect(p, end, '[');
+  ws(p, end);
+  if (p < end && *p == ']') {
+    ++p;
+  } else {
+    for (;;) {
+      RunsPlan::Run r;
+      expect(p, end, '[');
+      expect(p, end, '"');
+      r.prefix = p;
+      while (p < end && *p != '"') {
+        const unsigned char c = (unsigned char)*p;
+        if (c < 0x20 || c >= 0x80 || c == '\\') throw std::runtime_error("runs: bad prefix");
+        ++p;
+      }
+      r.prefix_len = (size_t)(p - r.prefix);
+      expect(p, end, '"');
+      expect(p, end, ',');
+      const uint64_t width = uint_field(p, end);
+      expect(p, end, ',');
+      r.start = uint_field(p, end);
+      expect(p, end, ',');
+      r.count = uint_field(p, end);
+      expect(p, end, ']');
+      if (width < 1 || width > kRunsMaxWidth) throw std::runtime_error("runs: bad width");
+      r.width = (unsigned)width;
+      if (r.count < 1 || r.count > left) throw std::runtime_error("runs: count mismatch");
+      left -= r.count;
+      // r.start, r.count < 10^18 each: the sum fits a uint64
+      if (r.start + r.count > kPow10[width]) throw std::runtime_error("runs: past the width");
+      // r.count <= kScratchCap from here on, so the product cannot wrap
+      if (r.count > kScratchCap) throw std::runtime_error("runs: too large");
+      const uint64_t per = (uint64_t)r.prefix_len + width + 3;  // quotes, comma
+      if (per > kScratchCap || r.count * per > kScratchCap - plan.total)
+        throw std::runtime_error("runs: too large");
+      plan.total += (size_t)(r.count * per);
+      plan.runs.push_back(r);
+      ws(p, end);
+      if (p < end && *p == ',') {
+        ++p;
+        continue;
+      }
+      expect(p, end, ']');
+      break;
+    }
+    plan.total -= 1;  // no comma after the last ID
+  }
+  ws(p, end);
+  if (p != end) throw std::runtime_error("runs: trailing bytes");
+  if (left) throw std::runtime_error("runs: count mismatch");
+  return plan;
+}
+
+// the literal list fragment, json.dumps(ids, separators=(",", ":")), into
+// out[0, plan.total)
+inline void write_runs(const RunsPlan& plan, char* out) {
+  char* q = out;
+  *q++ = '[';
+  bool first = true;
+  for (const RunsPlan::Run& r : plan.runs) {
+    char digits[kRunsMaxWidth];
+    uint64_t v = r.start;
+    for (unsigned i = r.width; i-- > 0;) {
+      digits[i] = (char)('0' + v % 10);
+      v /= 10;
+    }
+    for (uint64_t k = 0; k < r.count; ++k) {
+      if (!first) *q++ = ',';
+      first = false;
+      *q++ = '"';
+      memcpy(q, r.prefix, r.prefix_len);
+      q += r.prefix_len;
+      memcpy(q, digits, r.width);
+      q += r.width;
+      *q++ = '"';
+      for (unsigned i = r.width; i-- > 0;) {  // digits += 1
+        if (digits[i] != '9') {
+          ++digits[i];
+          break;
+        }
+        digits[i] = '0';
+      }
+    }
+  }
+  *q++ = ']';
+  if ((size_t)(q - out) != plan.total) throw std::logic_error("runs: size mismatch");
+}
+
+inline std::string expand_runs(const char* frag, size_t len, uint64_t expected_count) {
+  RunsPlan plan = parse_runs(frag, len, expected_count);
+  std::string out(plan.total, '\0');
+  write_runs(plan, &out[0]);
+  return out;
 }
 
 }  // namespace wirecore

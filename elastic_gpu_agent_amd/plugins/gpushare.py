@@ -263,7 +263,12 @@ class GPUSharePluginBase:
     def pre_start_container(self, request, context) -> dict:
         ids = request.get("devicesIDs", [])
         h8 = request.get("device_hash")
-        if h8 is not None and "list_json" in request:
+        if h8 is not None and "list_runs" in request:
+            # digest3: a large consecutive set as ID runs; its literal list
+            # is never built on the hot path
+            device = Device.from_runs(h8, request["device_count"],
+                                      request["list_runs"], self.resource_name)
+        elif h8 is not None and "list_json" in request:
             # digest2: hash + count + pre-serialized sorted list (no Python
             # string materialization on the hot path)
             device = Device.from_digest(h8, request["device_count"],

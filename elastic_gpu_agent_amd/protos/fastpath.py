@@ -134,6 +134,12 @@ def decode_prestart_request_digest(buf: bytes) -> dict:
     pre-serialized as a JSON fragment, all from one C++ pass. The handler
     persists the fragment verbatim (Device.from_digest), so at the 1-MiB
     contract unit the ~295k IDs never materialize as Python strings."""
+    if _fastwire is not None and hasattr(_fastwire, "decode_prestart_digest3"):
+        # a large set of consecutive IDs comes back as its runs fragment and
+        # the ~200 KB literal list is never built (see ids_to_runs)
+        h, n, frag, is_runs = _fastwire.decode_prestart_digest3(buf)
+        return {"devicesIDs": [], "device_hash": h, "device_count": n,
+                "list_runs" if is_runs else "list_json": frag}
     if _fastwire is not None and hasattr(_fastwire, "decode_prestart_digest2"):
         h, n, list_json = _fastwire.decode_prestart_digest2(buf)
         return {"devicesIDs": [], "device_hash": h, "device_count": n,
@@ -142,6 +148,113 @@ def decode_prestart_request_digest(buf: bytes) -> dict:
         ids, h = _fastwire.decode_prestart_digest(buf)
         return {"devicesIDs": ids, "device_hash": h}
     return decode_prestart_request(buf)
+
+
+# ---- ID runs: how the store keeps a large device set -----------------------
+# A sorted set of mostly consecutive IDs ("0-000000" .. "0-018431") is kept as
+# [[prefix, width, start, count], ...] instead of its literal list. The rules
+# (native/wirecore.h, "ID runs"): an ID is run-encodable when it ends in a
+# maximal run of 1..18 ASCII digits and holds no byte json.dumps would escape;
+# an ID with the prefix and width of its predecessor and value == previous + 1
+# extends the run, anything else starts one; a set is stored as runs only
+# when every ID is run-encodable, it has >= RUNS_MIN_IDS IDs and at most
+# count / RUNS_PER_IDS runs. The pure-Python versions below give the same
+# bytes as the native ones (tests/test_record_runs.py).
+RUNS_MIN_IDS = 1024
+RUNS_PER_IDS = 8
+RUNS_MAX_WIDTH = 18
+RUNS_MAX_EXPANDED = 4 << 20  # wirecore.h kScratchCap
+
+
+def _split_run_id(s: str):
+    """(prefix, width, value) of a run-encodable ID, else None."""
+    n = len(s)
+    w = 0
+    while w < n and "0" <= s[n - 1 - w] <= "9":
+        w += 1
+    if w == 0 or w > RUNS_MAX_WIDTH:
+        return None
+    prefix = s[:n - w]
+    for ch in prefix:
+        if ch < " " or ch > "\x7f" or ch in '"\\':
+            return None
+    return prefix, w, int(s[n - w:])
+
+
+def _py_ids_to_runs(sorted_ids):
+    n = len(sorted_ids)
+    if n < RUNS_MIN_IDS:
+        return None
+    runs = []
+    last = None  # (prefix, width, next value)
+    for s in sorted_ids:
+        t = _split_run_id(s)
+        if t is None:
+            return None
+        if last is not None and t == last:
+            runs[-1][3] += 1
+        else:
+            if len(runs) >= n // RUNS_PER_IDS:
+                return None
+            runs.append([t[0], t[1], t[2], 1])
+        last = (t[0], t[1], t[2] + 1)
+    import json
+
+    return json.dumps(runs, separators=(",", ":")).encode()
+
+
+def _py_expand_runs(frag: bytes, count: int) -> bytes:
+    import json
+
+    if b"\\" in frag:  # prefixes are stored unescaped
+        raise RuntimeError("runs: bad prefix")
+    try:
+        runs = json.loads(frag.decode("ascii"))
+    except ValueError as e:
+        raise RuntimeError(f"runs: malformed fragment: {e}") from None
+    if not isinstance(runs, list) or count < 0:
+        raise RuntimeError("runs: malformed fragment")
+    left, total = count, 2
+    for r in runs:
+        if not (isinstance(r, list) and len(r) == 4 and isinstance(r[0], str)
+                and all(type(x) is int and x >= 0 for x in r[1:])):
+            raise RuntimeError("runs: malformed fragment")
+        prefix, width, start, n = r
+        if any(ch < " " or ch > "\x7f" or ch in '"\\' for ch in prefix):
+            raise RuntimeError("runs: bad prefix")
+        if not 1 <= width <= RUNS_MAX_WIDTH:
+            raise RuntimeError("runs: bad width")
+        if n < 1 or n > left:
+            raise RuntimeError("runs: count mismatch")
+        left -= n
+        if start + n > 10 ** width:
+            raise RuntimeError("runs: past the width")
+        total += n * (len(prefix) + width + 3)
+        if total > RUNS_MAX_EXPANDED:
+            raise RuntimeError("runs: too large")
+    if left:
+        raise RuntimeError("runs: count mismatch")
+    parts = []
+    for prefix, width, start, n in runs:
+        parts.extend(f'"{prefix}{v:0{width}d}"' for v in range(start, start + n))
+    return ("[" + ",".join(parts) + "]").encode()
+
+
+def ids_to_runs(sorted_ids):
+    """Runs fragment of an already sorted ID list, or None when the set does
+    not qualify and keeps its literal list."""
+    if _fastwire is not None and hasattr(_fastwire, "ids_to_runs"):
+        return _fastwire.ids_to_runs(list(sorted_ids))
+    return _py_ids_to_runs(sorted_ids)
+
+
+def expand_runs(frag: bytes, count: int) -> bytes:
+    """Runs fragment + the record's ID count -> the literal list fragment,
+    json.dumps(ids, separators=(",", ":")). Raises on a fragment that does
+    not describe exactly ``count`` IDs."""
+    if _fastwire is not None and hasattr(_fastwire, "expand_runs"):
+        return _fastwire.expand_runs(frag, count)
+    return _py_expand_runs(frag, count)
 
 
 # Precomputable per-GPU Device suffix: health + topology are identical for

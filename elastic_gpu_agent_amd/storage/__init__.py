@@ -34,7 +34,13 @@ class Storage:
     that made 4 handler threads SLOWER than 1 (measured 0.77×) disappears.
     """
 
-    def __init__(self, db_path: str):
+    def __init__(self, db_path: str, record_format: str = "runs"):
+        if record_format not in ("runs", "list"):
+            raise ValueError(f"record format {record_format!r}: want runs or list")
+        # "runs": a large consecutive device set is kept as ID runs
+        # (PodInfo.stored_val); "list": every row is the reference-format
+        # record, as builds before the runs form wrote and read it
+        self._record_format = record_format
         db_dir = os.path.dirname(os.path.abspath(db_path))
         os.makedirs(db_dir, exist_ok=True)
         self._path = db_path
@@ -188,11 +194,30 @@ class Storage:
         self._submit([
             ("INSERT INTO pods(key, val) VALUES(?, ?) "
              "ON CONFLICT(key) DO UPDATE SET val=excluded.val",
-             (pod_info.key(), pod_info.val())),
+             (pod_info.key(), pod_info.stored_val()
+              if self._record_format == "runs" else pod_info.val())),
             ("INSERT INTO aux(key, val) VALUES(?, ?) "
              "ON CONFLICT(key) DO UPDATE SET val=excluded.val",
              (self.SUMMARY_PREFIX + pod_info.key(), self._summary(pod_info))),
         ])
+
+    def rewrite_as_lists(self) -> int:
+        """Rewrite every row that holds ID runs as the reference-format
+        record, so that a build from before the runs form can read the file.
+        Returns the rows rewritten."""
+        with self._lock:
+            rows = self._conn.execute(
+                "SELECT key, val FROM pods WHERE instr(val, ?) > 0", (b'"Runs":',)
+            ).fetchall()
+        n = 0
+        for key, val in rows:
+            literal = PodInfo.from_raw(key, val).val()
+            if literal != bytes(val):
+                # only the row that was read: a save in between wins
+                self._submit([("UPDATE pods SET val=? WHERE key=? AND val=?",
+                               (literal, key, val))])
+                n += 1
+        return n
 
     def load(self, namespace: str, name: str) -> PodInfo:
         key = f"{namespace}/{name}"
@@ -320,7 +345,7 @@ def migrate_from_bolt(bolt_path: str, storage: Storage) -> int:
     return n
 
 
-def new_storage(db_path: str) -> Storage:
+def new_storage(db_path: str, record_format: str = "runs") -> Storage:
     """Open the store; if ``db_path`` holds a BoltDB file from the reference
     agent, migrate it in place (the original is kept with a ``.bolt-bak``
     suffix).
@@ -360,5 +385,9 @@ def new_storage(db_path: str) -> Storage:
                 os.unlink(tmp + suffix)
             except FileNotFoundError:
                 pass
-        return Storage(db_path)
-    return Storage(db_path)
+        return Storage(db_path, record_format)
+    st = Storage(db_path, record_format)
+    if record_format == "list":
+        # the way back to a build that cannot read runs: leave none behind
+        st.rewrite_as_lists()
+    return st

@@ -13,6 +13,8 @@ import json
 from dataclasses import dataclass, field
 from typing import Dict, Iterable, List
 
+from .protos import fastpath
+
 
 def hash_device_ids(sorted_ids: List[str]) -> str:
     return hashlib.sha256(":".join(sorted_ids).encode()).hexdigest()[:8]
@@ -27,13 +29,20 @@ class Device:
     sorted list pre-serialized as a JSON array fragment instead of Python
     strings. Such a Device carries ``list_json`` + ``count`` with an empty
     ``list``; ``n_ids`` abstracts over both forms and ``val()`` splices the
-    fragment verbatim into the on-disk record."""
+    fragment verbatim into the reference-format record.
+
+    A large set of consecutive IDs arrives (decode_prestart_digest3) and is
+    stored as ``runs_json`` + ``count``: [[prefix, width, start, count], ...]
+    (fastpath.ids_to_runs). ``ids()``, ``to_json_obj()`` and
+    ``to_json_bytes()`` expand it on demand and stay reference-format;
+    ``to_stored_bytes()`` is what the store's own rows hold."""
 
     hash: str
     list: tuple
     resource_name: str
     count: int = -1          # -1 → len(list)
     list_json: bytes = b""   # pre-serialized sorted JSON array (C++ digest)
+    runs_json: bytes = b""   # the same set as ID runs, compact JSON
 
     @staticmethod
     def new(device_ids: Iterable[str], resource_name: str = "") -> "Device":
@@ -46,15 +55,27 @@ class Device:
         return Device(hash=h, list=(), resource_name=resource_name,
                       count=count, list_json=list_json)
 
+    @staticmethod
+    def from_runs(h: str, count: int, runs_json: bytes,
+                  resource_name: str = "") -> "Device":
+        return Device(hash=h, list=(), resource_name=resource_name,
+                      count=count, runs_json=runs_json)
+
     @property
     def n_ids(self) -> int:
         return self.count if self.count >= 0 else len(self.list)
 
+    def _list_fragment(self) -> bytes:
+        """The sorted IDs as a JSON array fragment (digest and runs forms)."""
+        if self.runs_json:
+            return fastpath.expand_runs(self.runs_json, self.count)
+        return self.list_json
+
     def ids(self) -> tuple:
         """Materialized sorted ID tuple (lazily decoded for digest form)."""
-        if self.list or not self.list_json:
+        if self.list or not (self.list_json or self.runs_json):
             return self.list
-        return tuple(json.loads(self.list_json))
+        return tuple(json.loads(self._list_fragment()))
 
     def equals(self, other: "Device") -> bool:
         return (
@@ -71,15 +92,43 @@ class Device:
     def to_json_bytes(self) -> bytes:
         """Record bytes; splices the pre-serialized list when present
         (byte-identical to json.dumps of to_json_obj)."""
-        if self.list_json and not self.list:
+        if (self.list_json or self.runs_json) and not self.list:
             return (b'{"Hash":' + json.dumps(self.hash).encode()
-                    + b',"List":' + self.list_json
+                    + b',"List":' + self._list_fragment()
                     + b',"ResourceName":' + json.dumps(self.resource_name).encode()
                     + b"}")
         return json.dumps(self.to_json_obj(), separators=(",", ":")).encode()
 
+    def to_stored_bytes(self) -> bytes:
+        """What the store's row holds: {"Hash","Runs","N","ResourceName"} for
+        a set that qualifies as runs, to_json_bytes() for every other."""
+        runs = self.runs_json
+        if not runs and len(self.list) >= fastpath.RUNS_MIN_IDS:
+            runs = fastpath.ids_to_runs(self.list)
+        if not runs:
+            return self.to_json_bytes()
+        return (b'{"Hash":' + json.dumps(self.hash).encode()
+                + b',"Runs":' + runs
+                + b',"N":' + str(self.n_ids).encode()
+                + b',"ResourceName":' + json.dumps(self.resource_name).encode()
+                + b"}")
+
     @staticmethod
     def from_json_obj(obj: dict) -> "Device":
+        if "Runs" in obj:
+            runs, n = obj["Runs"], obj.get("N")
+            if type(n) is not int or n < 0 or not isinstance(runs, list):
+                raise ValueError("runs record: bad N or Runs")
+            try:
+                total = sum(r[3] for r in runs)
+            except (TypeError, IndexError):
+                raise ValueError("runs record: malformed run") from None
+            if total != n:
+                raise ValueError(f"runs record: N={n} but the runs hold {total}")
+            return Device.from_runs(
+                obj.get("Hash", ""), n,
+                json.dumps(runs, separators=(",", ":")).encode(),
+                obj.get("ResourceName", ""))
         return Device(
             hash=obj.get("Hash", ""),
             list=tuple(obj.get("List") or ()),
@@ -116,6 +165,14 @@ class PodInfo:
         parts = []
         for c, d in self.container_device_map.items():
             parts.append(json.dumps(c).encode() + b":" + d.to_json_bytes())
+        return b"{" + b",".join(parts) + b"}"
+
+    def stored_val(self) -> bytes:
+        """The store's row: val() with each large consecutive set held as
+        runs (Device.to_stored_bytes). Equal to val() when no set qualifies."""
+        parts = []
+        for c, d in self.container_device_map.items():
+            parts.append(json.dumps(c).encode() + b":" + d.to_stored_bytes())
         return b"{" + b",".join(parts) + b"}"
 
     @staticmethod

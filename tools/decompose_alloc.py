@@ -2,7 +2,9 @@
 with the process's minor page faults, system time and voluntary context
 switches per call (getrusage) next to the wall times. The sha256 row (hashlib
 over the joined IDs) is the floor of the digest rows; the shuffled rows are
-what kubelet's unsorted lists cost.
+what kubelet's unsorted lists cost. decode_prestart_digest3 is what PreStart
+calls (a large consecutive set comes back as ID runs); expand_runs is what a
+reader of the stored record pays to get the list back.
 
   python tools/decompose_alloc.py              # 18,432 IDs: the mixed config
   python tools/decompose_alloc.py --ids 73728  # a 72-GiB pod at 1-MiB units
@@ -52,6 +54,11 @@ t("digest_allocate_request (C++ alone)", lambda: _fastwire.digest_allocate_reque
 t("digest_allocate_request, shuffled IDs", lambda: _fastwire.digest_allocate_request(enc_shuf))
 t("decode_prestart_digest2 (C++ alone)", lambda: _fastwire.decode_prestart_digest2(pre_enc))
 t("decode_prestart_digest2, shuffled IDs", lambda: _fastwire.decode_prestart_digest2(pre_enc_shuf))
+t("decode_prestart_digest3 (C++ alone)", lambda: _fastwire.decode_prestart_digest3(pre_enc))
+t("decode_prestart_digest3, shuffled IDs", lambda: _fastwire.decode_prestart_digest3(pre_enc_shuf))
+_, _n, _frag, _is_runs = _fastwire.decode_prestart_digest3(pre_enc)
+if _is_runs:  # what a reader of the stored record pays to get the list back
+    t("expand_runs (runs -> list fragment)", lambda: _fastwire.expand_runs(_frag, _n))
 t("wire+server full (pre-encoded)", lambda: raw(enc))
 small = fastpath.encode_allocate_request({"container_requests":[{"devicesIDs": ids[:20]}]})
 t("wire+server (20 ids)", lambda: raw(small))

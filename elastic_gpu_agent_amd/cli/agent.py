@@ -53,6 +53,10 @@ def main(argv=None) -> int:
                              "set: as ID runs, or as the literal list that "
                              "builds before the runs form read (use list "
                              "before rolling back to such a build)")
+    parser.add_argument("--hashMemoEntries", type=int, default=256,
+                        help="device sets whose hash Allocate keeps for the "
+                             "PreStart that follows, so a large set is hashed "
+                             "once per bind instead of twice (0 = off)")
     # path overrides (defaults match the DaemonSet mounts; overridable for
     # local runs and tests)
     parser.add_argument("--plugin-dir", default=None, help="kubelet device-plugins dir")
@@ -107,6 +111,7 @@ def main(argv=None) -> int:
         selftest_seconds=args.gpu_selftest_seconds,
         selftest_timeout=args.gpu_selftest_timeout,
         record_format=args.recordFormat,
+        hash_memo_entries=args.hashMemoEntries,
     )
     manager = GPUManager(opts)
     manager.run()

@@ -25,6 +25,11 @@ from .. import consts
 from ..types import GPUDevice
 from .cumask import mask_hex, mask_words_from_cus, parse_mask_hex
 
+try:
+    from .._fastwire import atomic_write as _native_atomic_write
+except ImportError:  # pure-Python fallback in LimitsWriter._atomic_write
+    _native_atomic_write = None
+
 AUX_MASK_PREFIX = "mask/"  # aux key: mask/<alloc_hash> -> json record
 
 # QoS rank order: reclaim flows strictly downhill (a high-priority pod may
@@ -597,6 +602,11 @@ class LimitsWriter:
         # unique temp name: concurrent writers of the SAME allocation (e.g. a
         # kubelet retry racing the first attempt) must not clobber each
         # other's temp file (found by tools/soak.py)
+        if _native_atomic_write is not None:
+            # temp file, write and rename in one GIL-free call
+            # (native/bindfx.h); json.dumps gives json.dump's bytes
+            _native_atomic_write(path, json.dumps(obj).encode())
+            return
         import tempfile
 
         fd, tmp = tempfile.mkstemp(dir=os.path.dirname(path), suffix=".tmp")

@@ -47,6 +47,9 @@ class ManagerOptions:
     # (ID runs) or "list" (the reference-format record; the way back for a
     # rollback to a build that cannot read runs)
     record_format: str = "runs"
+    # entry cap of the native Allocate -> PreStart hash memo (0 = off); each
+    # process, pre-forked workers included, keeps its own
+    hash_memo_entries: int = 256
 
     def to_json(self) -> str:
         import dataclasses
@@ -71,7 +74,10 @@ class GPUManager:
             raise ValueError(f"unsupported plugin {opts.gpu_plugin_name!r} (only 'gpushare')")
         self.opts = opts
 
+        from .protos import fastpath
         from .storage import new_storage
+
+        fastpath.hash_memo_configure(opts.hash_memo_entries)
 
         self.storage = storage or new_storage(opts.db_path, opts.record_format)
 

@@ -109,6 +109,18 @@ class Metrics:
                     for k, v in summ.items():
                         g.add_metric([name, k], v)
                 yield g
+                # Allocate -> PreStart hash memo of this process (hits are
+                # sha256 passes PreStart did not repeat)
+                from .protos import fastpath
+
+                memo = fastpath.hash_memo_stats()
+                if memo:
+                    m = GaugeMetricFamily(
+                        "egpu_hash_memo", "device-set hash memo counters", labels=["k"]
+                    )
+                    for k, v in memo.items():
+                        m.add_metric([k], v)
+                    yield m
 
         REGISTRY.register(_Collector())
         start_http_server(port)

@@ -1,7 +1,8 @@
 """Build + (optionally) run the libFuzzer harness over the native parsers,
 and the stand-alone sanitizer self-tests of the device-set digest, of the
-ID-run codec the store uses, of the GPU self-test's host reference and of the
-transport's HTTP/2 framing core.
+ID-run codec the store uses, of the GPU self-test's host reference, of the
+transport's HTTP/2 framing core, of the Allocate -> PreStart hash memo and of
+the native file effects of a bind.
 
 Usage:
   python -m elastic_gpu_agent_amd.native.build_fuzz             # build only
@@ -11,7 +12,9 @@ Usage:
                                                                 # (general, then fixed-stride/radix),
                                                                 # then the ID-run codec,
                                                                 # then selftest_ref.h,
-                                                                # then h2frame.h
+                                                                # then h2frame.h,
+                                                                # then the hash memo,
+                                                                # then bindfx.h
 """
 from __future__ import annotations
 
@@ -114,13 +117,30 @@ def build_h2frame_selftest(out=None):
     return build_selftest(out, "h2frame_selftest.cpp")
 
 
+def build_hash_memo_selftest(out=None):
+    """hash_memo_selftest.cpp: wirecore.h's HashMemo and the two digests that
+    share it, threaded case included, built the same way."""
+    out = out or os.path.join(REPO, "bin", "egpu-hash-memo-selftest")
+    return build_selftest(out, "hash_memo_selftest.cpp")
+
+
+def build_bindfx_selftest(out=None):
+    """bindfx_selftest.cpp: the symlink / temp-file-and-rename / unlink calls
+    of bindfx.h in a scratch directory, threaded case included, built the
+    same way."""
+    out = out or os.path.join(REPO, "bin", "egpu-bindfx-selftest")
+    return build_selftest(out, "bindfx_selftest.cpp")
+
+
 if __name__ == "__main__":
     if "--selftest" in sys.argv:
         rc = subprocess.call([build_selftest()])
         rc = rc or subprocess.call([build_stride_selftest()])
         rc = rc or subprocess.call([build_runs_selftest()])
         rc = rc or subprocess.call([build_ref_selftest()])
-        sys.exit(rc or subprocess.call([build_h2frame_selftest()]))
+        rc = rc or subprocess.call([build_h2frame_selftest()])
+        rc = rc or subprocess.call([build_hash_memo_selftest()])
+        sys.exit(rc or subprocess.call([build_bindfx_selftest()]))
     binary = build()
     if "--replay" in sys.argv:
         sys.exit(replay(binary))

@@ -23,11 +23,19 @@
 #include <openssl/evp.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdint>
 #include <cstring>
+#include <iterator>
+#include <list>
+#include <mutex>
 #include <stdexcept>
 #include <string>
+#include <string_view>
+#include <unordered_map>
 #include <vector>
+
+#include "bindfx.h"
 
 namespace py = pybind11;
 
@@ -163,6 +171,10 @@ using wirecore::DigestScratch;
 using wirecore::ScratchGuard;
 using wirecore::Span;
 
+// fragment -> hash of the large sets Allocate has digested and PreStart has
+// not yet taken (wirecore.h, "hash memo"); one per process
+wirecore::HashMemo g_hash_memo;
+
 std::vector<std::pair<std::string, size_t>> digest_raw(const uint8_t* p, size_t len) {
   // container requests are few (one per container); only the per-container
   // ID walk is hot
@@ -173,8 +185,8 @@ std::vector<std::pair<std::string, size_t>> digest_raw(const uint8_t* p, size_t 
   DigestScratch& sc = wirecore::digest_scratch();
   for (auto& o : outer) {
     ScratchGuard guard(sc);
-    DigestOut d = wirecore::digest_field(sc, o.first, o.second, 1, false, false,
-                                         sha256_evp);
+    DigestOut d = wirecore::digest_field_put(sc, o.first, o.second, 1, sha256_evp,
+                                             &g_hash_memo);
     result.emplace_back(std::string(d.hex, 8), d.count);
   }
   return result;
@@ -242,7 +254,9 @@ py::tuple decode_prestart_digest2(py::bytes data) {
 // its runs fragment ([[prefix, width, start, count], ...], is_runs = True)
 // and its literal list is never built: the store keeps the runs, and
 // expand_runs rebuilds the list for the few readers that want it. Sets that
-// do not qualify (wirecore.h, "ID runs") come back exactly as from v2.
+// do not qualify (wirecore.h, "ID runs") come back exactly as from v2. A set
+// that qualifies and was digested by Allocate just before takes its hash
+// from the memo instead of hashing the same bytes again.
 py::tuple decode_prestart_digest3(py::bytes data) {
   char* buf;
   Py_ssize_t len;
@@ -253,11 +267,28 @@ py::tuple decode_prestart_digest3(py::bytes data) {
   bool is_runs = false;
   {
     py::gil_scoped_release rel;
-    d = wirecore::digest_field_runs(sc, (const uint8_t*)buf, (size_t)len, 1, sha256_evp,
-                                    &is_runs);
+    d = wirecore::digest_field_runs_take(sc, (const uint8_t*)buf, (size_t)len, 1,
+                                         sha256_evp, &is_runs, &g_hash_memo);
   }
   return py::make_tuple(py::str(d.hex, 8), (long long)d.count,
                         py::bytes(sc.json.data(), d.json_len), is_runs);
+}
+
+void hash_memo_configure(long long entries) {
+  if (entries < 0) throw std::invalid_argument("hash memo: negative entry cap");
+  g_hash_memo.configure((size_t)entries);
+}
+
+py::dict hash_memo_stats() {
+  wirecore::HashMemoStats s = g_hash_memo.stats();
+  py::dict d;
+  d["puts"] = s.puts;
+  d["hits"] = s.hits;
+  d["misses"] = s.misses;
+  d["evictions"] = s.evictions;
+  d["entries"] = s.entries;
+  d["cap"] = s.cap;
+  return d;
 }
 
 // The runs fragment of an already sorted list of IDs (a Device built from
@@ -619,6 +650,46 @@ py::bytes encode_allocate_response(py::dict resp) {
   return py::bytes(out);
 }
 
+// ---- file effects of a bind and of a GC pass (bindfx.h) ----------------------
+// The arguments are copied out of the Python objects first; the syscalls run
+// with the GIL released. A failure becomes OSError with its errno and path.
+
+[[noreturn]] void raise_oserror(const bindfx::SysError& e) {
+  errno = e.err;
+  PyErr_SetFromErrnoWithFilename(PyExc_OSError, e.path.c_str());
+  throw py::error_already_set();
+}
+
+void make_links(const std::vector<std::pair<std::string, std::string>>& pairs) {
+  try {
+    py::gil_scoped_release rel;
+    bindfx::make_links(pairs);
+  } catch (const bindfx::SysError& e) {
+    raise_oserror(e);
+  }
+}
+
+void atomic_write(const std::string& path, py::bytes data) {
+  char* buf;
+  Py_ssize_t len;
+  PyBytes_AsStringAndSize(data.ptr(), &buf, &len);
+  try {
+    py::gil_scoped_release rel;
+    bindfx::atomic_write(path, buf, (size_t)len);
+  } catch (const bindfx::SysError& e) {
+    raise_oserror(e);
+  }
+}
+
+void unlink_many(const std::vector<std::string>& paths) {
+  try {
+    py::gil_scoped_release rel;
+    bindfx::unlink_many(paths);
+  } catch (const bindfx::SysError& e) {
+    raise_oserror(e);
+  }
+}
+
 }  // namespace
 
 PYBIND11_MODULE(_fastwire, m) {
@@ -638,4 +709,11 @@ PYBIND11_MODULE(_fastwire, m) {
   m.def("preferred_digest", &preferred_digest);
   m.def("podresources_digest", &podresources_digest);
   m.def("preferred_extract", &preferred_extract);
+  m.def("hash_memo_configure", &hash_memo_configure, py::arg("entries"));
+  m.def("hash_memo_stats", &hash_memo_stats);
+  m.attr("HASH_MEMO_ENTRIES") = (long long)wirecore::kMemoEntries;
+  m.attr("HASH_MEMO_MAX_KEY") = (long long)wirecore::kMemoMaxKey;
+  m.def("make_links", &make_links, py::arg("pairs"));
+  m.def("atomic_write", &atomic_write, py::arg("path"), py::arg("data"));
+  m.def("unlink_many", &unlink_many, py::arg("paths"));
 }

@@ -10,7 +10,9 @@
 //   3: AllocateRequest digest (outer field1 → wirecore.h digest_field per
 //      container: the fused walk/check/join/hash helper behind _fastwire),
 //      and the same set through digest_field_runs: where it comes back as ID
-//      runs, expanding them must give the literal list fragment
+//      runs, expanding them must give the literal list fragment; and once
+//      more through the Allocate and PreStart digests that share a hash memo:
+//      digest with memo == digest without
 //   4: minijson parse (OCI config/state parsing in egpu-hook); the same
 //      bytes, read as a 16-bit ID count and a runs fragment, through
 //      wirecore.h expand_runs (what the store reads back)
@@ -111,6 +113,26 @@ void fuzz_wire_nested(const uint8_t* data, size_t size) {
       } else if (json_no_spans != std::string(sc.json.data(), r.json_len)) {
         __builtin_trap();
       }
+      // hash memo: Allocate's digest puts, PreStart's takes (or hashes); the
+      // second PreStart finds the entry consumed. All equal the plain ones.
+      const std::string runs_json(sc.json.data(), r.json_len);
+      static wirecore::HashMemo memo;
+      const uint64_t hits = memo.stats().hits;
+      wirecore::DigestOut a =
+          wirecore::digest_field_put(sc, o.first, o.second, 1, sum_digest, &memo);
+      if (hex_no_spans != a.hex || a.count != count) __builtin_trap();
+      for (int pass = 0; pass < 2; ++pass) {
+        bool memo_runs = false;
+        wirecore::DigestOut t = wirecore::digest_field_runs_take(
+            sc, o.first, o.second, 1, sum_digest, &memo_runs, &memo);
+        if (hex_no_spans != t.hex || t.count != count || memo_runs != is_runs)
+          __builtin_trap();
+        if (runs_json != std::string(sc.json.data(), t.json_len)) __builtin_trap();
+      }
+      // a hit needs a set that qualifies with a fragment within the key cap
+      const bool storable = is_runs && runs_json.size() <= wirecore::kMemoMaxKey;
+      if (memo.stats().hits - hits != (storable ? 1u : 0u)) __builtin_trap();
+      if (memo.stats().entries != 0) __builtin_trap();
     }
   } catch (const std::runtime_error&) {
   }

@@ -4,10 +4,16 @@
 #pragma once
 
 #include <algorithm>
+#include <atomic>
 #include <cstdint>
 #include <cstring>
+#include <iterator>
+#include <list>
+#include <mutex>
 #include <stdexcept>
 #include <string>
+#include <string_view>
+#include <unordered_map>
 #include <utility>
 #include <vector>
 
@@ -229,9 +235,10 @@ struct IdRun {
 
 // Fed the sorted IDs one by one. The expected successor is kept as text, so
 // an ID that extends the run costs one compare and an ASCII increment. The
-// digest's word-at-a-time loops see "previous ID + 1 in the last digit, no
-// carry" on the words they already hold and only report how many such IDs
-// went by (extend).
+// digest's word-at-a-time loops see "previous ID + 1 in the last digit" and
+// "previous ID + 1 with one carry (x9 -> y0)" on the words they already hold
+// and only report how many such IDs went by and the last of them (extend), so
+// 99 of 100 consecutive IDs never reach add.
 struct RunBuilder {
   std::vector<IdRun> runs;
   std::string prefixes;
@@ -265,13 +272,14 @@ struct RunBuilder {
     has_next = false;
   }
 
-  // the last run grew by k IDs, each its predecessor with the last digit
-  // one higher (so k <= 9 and `next` is the first of them)
-  void extend(size_t k) {
+  // the last run grew by k IDs, each the decimal successor of the one before
+  // it within the run's digits, the first of them being `next`; `last` is
+  // the k-th
+  void extend(size_t k, const uint8_t* last, size_t len) {
     if (!k || !ok || !has_next) return;
     runs.back().count += k;
     n += k;
-    next[next.size() - 1] = (char)(next[next.size() - 1] + (char)(k - 1));
+    next.assign((const char*)last, len);
     advance();
   }
 
@@ -357,7 +365,7 @@ struct DigestScratch {
   std::string json;
   std::vector<Span> spans;
   std::vector<uint64_t> keys;  // radix fallback: n keys + n for the passes
-  RunBuilder runs;             // digest_field_runs only
+  RunBuilder runs;             // digest_field_runs and the two memo digests
 
   void trim() {
     if (joined.capacity() > kScratchCap) std::string().swap(joined);
@@ -421,8 +429,21 @@ inline char* json_put_string(char* out, const uint8_t* sp, size_t n) {
 struct DigestOut {
   char hex[9];
   size_t count;
-  size_t json_len;  // bytes of scratch.json holding the fragment
+  size_t json_len;    // bytes of scratch.json holding the fragment
+  size_t joined_len;  // bytes of scratch.joined holding the ':'-joined IDs
 };
+
+// the first 8 hex characters of sha(data[0, len)), NUL-terminated
+inline void hash_hex8(Sha256Fn sha, const void* data, size_t len, char hex[9]) {
+  unsigned char md[32];
+  sha(data, len, md);
+  static const char kHex[] = "0123456789abcdef";
+  for (int i = 0; i < 4; ++i) {
+    hex[2 * i] = kHex[md[i] >> 4];
+    hex[2 * i + 1] = kHex[md[i] & 15];
+  }
+  hex[8] = 0;
+}
 
 // writer over the two scratch strings; keeps its cursors in locals
 struct DigestWriter {
@@ -517,6 +538,9 @@ struct DigestWriter {
     if (L <= 8) {
       const int sh = 64 - 8 * (int)L;
       const uint64_t unit = 1ull << sh;
+      // x9 -> y0 in the last two bytes: + 256 units - 9 units
+      const uint64_t carry = 247 * unit;
+      const int sh1 = L >= 2 ? sh + 8 : sh;  // the digit before the last
       const uint64_t mask = ~0ull << (64 - 8 * L);
       // the bytes past the ID must not look like bytes to escape
       const uint64_t pad = ~mask & 0x3030303030303030ull;
@@ -534,10 +558,14 @@ struct DigestWriter {
           break;
         }
         if (rbl) {
-          if (key - pk == unit && (unsigned)(((pk >> sh) & 0xFF) - '0') < 9) {
+          const uint64_t d = key - pk;
+          const unsigned d0 = (unsigned)((pk >> sh) & 0xFF) - '0';
+          if ((d == unit && d0 < 9) ||
+              (d == carry && d0 == 9 && L >= 2 &&
+               (unsigned)(((pk >> sh1) & 0xFF) - '0') < 9)) {
             ++matched;
           } else {
-            rbl->extend(matched);
+            rbl->extend(matched, last, L);
             matched = 0;
             rbl->add(pay, L);
             if (!rbl->ok) rbl = nullptr;
@@ -586,10 +614,14 @@ struct DigestWriter {
           break;
         }
         if (rbl) {
-          if (kh == ph && kl - pl == 1 && (unsigned)((pl & 0xFF) - '0') < 9) {
+          const uint64_t d = kl - pl;
+          const unsigned d0 = (unsigned)(pl & 0xFF) - '0';
+          if (kh == ph && ((d == 1 && d0 < 9) ||
+                           (d == 247 && d0 == 9 &&
+                            (unsigned)(((pl >> 8) & 0xFF) - '0') < 9))) {
             ++matched;
           } else {
-            rbl->extend(matched);
+            rbl->extend(matched, last, L);
             matched = 0;
             rbl->add(pay, L);
             if (!rbl->ok) rbl = nullptr;
@@ -623,7 +655,7 @@ struct DigestWriter {
         p += stride;
       }
     }
-    if (rbl) rbl->extend(matched);
+    if (rbl) rbl->extend(matched, last, L);
     jo = j;
     js = q;
     r.p = p;
@@ -645,6 +677,9 @@ struct DigestWriter {
     size_t matched = 0;
     const int sh = 64 - 8 * (int)L;
     const uint64_t unit = 1ull << sh;
+    const uint64_t carry = 247 * unit;  // x9 -> y0, as in run()
+    const int sh1 = L >= 2 ? sh + 8 : sh;
+    uint8_t id[8];  // the previous key's bytes, when IDs went by uncounted
     for (size_t i = 0; i < n; ++i) {
       const uint64_t key = keys[i];
       const uint64_t raw = word_to_be(key);
@@ -652,14 +687,21 @@ struct DigestWriter {
       memcpy(j, &raw, 8);
       j += L;
       if (rbl) {
-        if (i && key - keys[i - 1] == unit &&
-            (unsigned)(((keys[i - 1] >> sh) & 0xFF) - '0') < 9) {
+        const uint64_t pk = i ? keys[i - 1] : 0;
+        const uint64_t d = key - pk;
+        const unsigned d0 = (unsigned)((pk >> sh) & 0xFF) - '0';
+        if (i && ((d == unit && d0 < 9) ||
+                  (d == carry && d0 == 9 && L >= 2 &&
+                   (unsigned)(((pk >> sh1) & 0xFF) - '0') < 9))) {
           ++matched;
         } else {
-          uint8_t id[8];
+          if (matched) {
+            const uint64_t praw = word_to_be(pk);
+            memcpy(id, &praw, 8);
+            rbl->extend(matched, id, L);
+            matched = 0;
+          }
           memcpy(id, &raw, 8);
-          rbl->extend(matched);
-          matched = 0;
           rbl->add(id, L);
           if (!rbl->ok) rbl = nullptr;
         }
@@ -680,7 +722,11 @@ struct DigestWriter {
         }
       }
     }
-    if (rbl) rbl->extend(matched);
+    if (rbl && matched) {
+      const uint64_t praw = word_to_be(keys[n - 1]);
+      memcpy(id, &praw, 8);
+      rbl->extend(matched, id, L);
+    }
     jo = j;
     js = q;
   }
@@ -696,15 +742,8 @@ struct DigestWriter {
     }
     out.hex[0] = 0;
     out.count = count;
-    if (!sha) return out;
-    unsigned char md[32];
-    sha(s.joined.data(), jo - &s.joined[0], md);
-    static const char kHex[] = "0123456789abcdef";
-    for (int i = 0; i < 4; ++i) {
-      out.hex[2 * i] = kHex[md[i] >> 4];
-      out.hex[2 * i + 1] = kHex[md[i] & 15];
-    }
-    out.hex[8] = 0;
+    out.joined_len = jo - &s.joined[0];
+    if (sha) hash_hex8(sha, s.joined.data(), out.joined_len, out.hex);
     return out;
   }
 };
@@ -847,6 +886,154 @@ inline DigestOut digest_field_runs(DigestScratch& s, const uint8_t* p, size_t le
     *is_runs = true;
     return d;
   }
+  DigestOut l = digest_ranges(s, &range, 1, want, true, false, nullptr);
+  d.json_len = l.json_len;
+  return d;
+}
+
+// ---- hash memo ----------------------------------------------------------------
+// Allocate and PreStart hash the same device set moments apart. For a set
+// that qualifies as runs, the runs fragment is an exact name of the sorted
+// list (expand_runs rebuilds it byte for byte), so equal fragments mean equal
+// joined bytes and equal hashes: Allocate leaves fragment -> hash here and
+// PreStart takes it instead of hashing again. A hit removes the entry, so
+// every skipped hash stands for one hash Allocate really computed.
+//
+// Bounds: at most `cap` entries (kMemoEntries by default, 0 = off), keys of
+// at most kMemoMaxKey bytes (a longer fragment is not stored and its PreStart
+// hashes), so the memo holds about 1 MiB of keys at the most. At the cap the
+// oldest entry goes. One mutex guards it: digests run without the GIL on
+// several server threads, and the critical sections are a lookup and a copy
+// of ~100 bytes.
+
+constexpr size_t kMemoEntries = 256;
+constexpr size_t kMemoMaxKey = 4096;
+
+struct HashMemoStats {
+  uint64_t puts = 0, hits = 0, misses = 0, evictions = 0;
+  size_t entries = 0, cap = 0;
+};
+
+class HashMemo {
+ public:
+  // 0 turns the memo off and empties it; a smaller cap drops the oldest
+  void configure(size_t entries) {
+    std::lock_guard<std::mutex> g(mu_);
+    cap_ = entries;
+    while (order_.size() > cap_) drop_oldest();
+  }
+
+  // unlocked peek for the callers' fast path; put and take check again
+  bool enabled() const { return cap_.load(std::memory_order_relaxed) != 0; }
+
+  void put(std::string_view key, const char hex[8]) {
+    if (key.size() > kMemoMaxKey) return;
+    std::lock_guard<std::mutex> g(mu_);
+    if (!cap_) return;
+    ++stats_.puts;
+    auto it = index_.find(key);
+    if (it != index_.end()) {
+      // the same set again: one entry, now the newest
+      memcpy(it->second->hex, hex, 8);
+      order_.splice(order_.end(), order_, it->second);
+      return;
+    }
+    if (order_.size() >= cap_) {
+      drop_oldest();
+      ++stats_.evictions;
+    }
+    order_.emplace_back();
+    Entry& e = order_.back();
+    e.key.assign(key.data(), key.size());
+    memcpy(e.hex, hex, 8);
+    index_.emplace(std::string_view(e.key), std::prev(order_.end()));
+  }
+
+  // on a hit copies the hash (NUL-terminated) and removes the entry
+  bool take(std::string_view key, char hex[9]) {
+    std::lock_guard<std::mutex> g(mu_);
+    if (!cap_) return false;
+    auto it = key.size() <= kMemoMaxKey ? index_.find(key) : index_.end();
+    if (it == index_.end()) {
+      ++stats_.misses;
+      return false;
+    }
+    ++stats_.hits;
+    memcpy(hex, it->second->hex, 8);
+    hex[8] = 0;
+    auto node = it->second;
+    index_.erase(it);  // before the node that owns the key's bytes
+    order_.erase(node);
+    return true;
+  }
+
+  HashMemoStats stats() {
+    std::lock_guard<std::mutex> g(mu_);
+    HashMemoStats s = stats_;
+    s.entries = order_.size();
+    s.cap = cap_;
+    return s;
+  }
+
+ private:
+  struct Entry {
+    std::string key;
+    char hex[8];
+  };
+
+  void drop_oldest() {
+    index_.erase(std::string_view(order_.front().key));
+    order_.pop_front();
+  }
+
+  std::mutex mu_;
+  std::atomic<size_t> cap_{kMemoEntries};
+  std::list<Entry> order_;  // oldest first; the index's keys view these nodes
+  std::unordered_map<std::string_view, std::list<Entry>::iterator> index_;
+  HashMemoStats stats_;
+};
+
+// Allocate side: digest_field(want_json = false) for a caller that feeds the
+// memo. A field large enough to hold a set that qualifies is walked with the
+// scratch RunBuilder, hashed as ever, and where the set does qualify its
+// fragment -> hash is put. The result never differs from digest_field's.
+inline DigestOut digest_field_put(DigestScratch& s, const uint8_t* p, size_t len,
+                                  uint32_t want, Sha256Fn sha, HashMemo* memo) {
+  if (len < 3 * kRunsMinIds || !memo || !memo->enabled())
+    return digest_field(s, p, len, want, false, false, sha);
+  Span range{p, len};
+  s.runs.reset(len / (3 * kRunsPerIds));
+  DigestOut d = digest_ranges(s, &range, 1, want, false, false, sha, &s.runs);
+  if (s.runs.qualifies() && s.runs.n == d.count) {
+    s.runs.to_json(s.json);
+    memo->put(s.json, d.hex);
+  }
+  return d;
+}
+
+// PreStart side: digest_field_runs for a caller that consults the memo. The
+// walk leaves the hash out; a set that qualifies takes its hash from the
+// memo, and on a miss the joined bytes the walk left in the scratch are
+// hashed. A set that does not qualify is hashed from those same bytes before
+// the second walk builds its list, so no set is walked more often than by
+// digest_field_runs and none is hashed twice.
+inline DigestOut digest_field_runs_take(DigestScratch& s, const uint8_t* p, size_t len,
+                                        uint32_t want, Sha256Fn sha, bool* is_runs,
+                                        HashMemo* memo) {
+  if (len < 3 * kRunsMinIds || !memo || !memo->enabled())
+    return digest_field_runs(s, p, len, want, sha, is_runs);
+  *is_runs = false;
+  Span range{p, len};
+  s.runs.reset(len / (3 * kRunsPerIds));
+  DigestOut d = digest_ranges(s, &range, 1, want, false, false, nullptr, &s.runs);
+  if (s.runs.qualifies() && s.runs.n == d.count) {
+    s.runs.to_json(s.json);
+    d.json_len = s.json.size();
+    *is_runs = true;
+    if (!memo->take(s.json, d.hex)) hash_hex8(sha, s.joined.data(), d.joined_len, d.hex);
+    return d;
+  }
+  hash_hex8(sha, s.joined.data(), d.joined_len, d.hex);
   DigestOut l = digest_ranges(s, &range, 1, want, true, false, nullptr);
   d.json_len = l.json_len;
   return d;

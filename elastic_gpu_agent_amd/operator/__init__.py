@@ -20,6 +20,12 @@ from typing import Dict, List, Optional
 from .. import consts
 from ..types import GPUDevice
 
+try:  # one GIL-free call for both links of a bind (native/bindfx.h)
+    from .._fastwire import make_links as _native_make_links
+    from .._fastwire import unlink_many as _native_unlink_many
+except ImportError:  # pure-Python fallback, same contract
+    _native_make_links = _native_unlink_many = None
+
 
 class GPUBackend(abc.ABC):
     """Enumerates physical (or synthetic) GPUs."""
@@ -36,6 +42,7 @@ class GPUOperator:
         self.backend = backend
         self.dev_root = dev_root
         self._cache: Optional[List[GPUDevice]] = None
+        self._root_made = False
 
     # ---- enumeration ----
     def devices(self, refresh: bool = False) -> List[GPUDevice]:
@@ -64,9 +71,20 @@ class GPUOperator:
         /dev/nvidiactl plays in the reference)."""
         dev = self.device_by_index(gpu_index)
         paths = self._link_paths(alloc_id)
-        os.makedirs(self.dev_root, exist_ok=True)
-        self._force_symlink(consts.DRI_RENDER_FMT % dev.drm_render_minor, paths["gpu"])
-        self._force_symlink(consts.KFD_PATH, paths["ctl"])
+        pairs = [
+            (consts.DRI_RENDER_FMT % dev.drm_render_minor, paths["gpu"]),
+            (consts.KFD_PATH, paths["ctl"]),
+        ]
+        # dev_root is made once, not per bind; if it has gone since, the
+        # links fail with ENOENT: make it again and retry once
+        if not self._root_made:
+            os.makedirs(self.dev_root, exist_ok=True)
+            self._root_made = True
+        try:
+            self._make_links(pairs)
+        except FileNotFoundError:
+            os.makedirs(self.dev_root, exist_ok=True)
+            self._make_links(pairs)
 
     def delete(self, gpu_index: int, alloc_id: str) -> None:
         """Remove the per-allocation symlinks. ``gpu_index`` may be -1 when the
@@ -77,9 +95,21 @@ class GPUOperator:
             except FileNotFoundError:
                 pass
 
+    def link_paths(self, alloc_id: str) -> List[str]:
+        """The paths ``delete`` would unlink (GC batches them)."""
+        return list(self._link_paths(alloc_id).values())
+
     def check(self, gpu_index: int, alloc_id: str) -> bool:
         paths = self._link_paths(alloc_id)
         return all(os.path.islink(p) for p in paths.values())
+
+    @classmethod
+    def _make_links(cls, pairs) -> None:
+        if _native_make_links is not None:
+            _native_make_links(pairs)
+        else:
+            for target, link in pairs:
+                cls._force_symlink(target, link)
 
     @staticmethod
     def _force_symlink(target: str, link: str) -> None:
@@ -101,3 +131,22 @@ class GPUOperator:
                 except FileNotFoundError:
                     pass
         raise OSError(f"could not materialize symlink {link} -> {target}")
+
+
+def unlink_many(paths) -> None:
+    """Unlink every path. A missing one is fine; the rest are all tried and
+    the first other error is raised afterwards."""
+    paths = list(paths)
+    if _native_unlink_many is not None:
+        _native_unlink_many(paths)
+        return
+    first = None
+    for p in paths:
+        try:
+            os.unlink(p)
+        except FileNotFoundError:
+            pass
+        except OSError as e:
+            first = first or e
+    if first is not None:
+        raise first

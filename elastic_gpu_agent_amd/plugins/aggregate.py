@@ -15,6 +15,7 @@ from typing import List
 
 from .. import consts
 from ..kube.client import NotFound
+from ..operator import unlink_many
 from ..types import PodInfo
 from .base import DevicePluginServer
 from .config import GPUPluginConfig
@@ -122,6 +123,10 @@ class GPUSharePlugin:
         import os
 
         aux_keys = []
+        # the links, limits files and pid files of the whole pass go in one
+        # unlink_many call instead of one Python try/unlink each
+        must_go: List[str] = []  # an error other than ENOENT fails the pass
+        pid_files: List[str] = []  # best effort
         for ns, name, summary in doomed:
             for container, dev in summary.items():
                 dhash, n_ids, resource = dev["h"], dev["n"], dev["r"]
@@ -131,17 +136,22 @@ class GPUSharePlugin:
                     else 1
                 )
                 for i in range(links):
-                    self.cfg.operator.delete(-1, f"{dhash}-{i}")
+                    must_go.extend(self.cfg.operator.link_paths(f"{dhash}-{i}"))
                 if self.cfg.cumask:
                     aux_keys.append("mask/" + dhash)
                 if self.cfg.limits:
-                    self.cfg.limits.delete(dhash)
-                try:  # hook-recorded pid file (occupancy attribution)
-                    os.unlink(
-                        os.path.join(self.cfg.paths.state_dir, "pids", dhash)
-                    )
-                except OSError:
-                    pass
+                    must_go.append(self.cfg.limits.host_path(dhash))
+                # hook-recorded pid file (occupancy attribution)
+                pid_files.append(
+                    os.path.join(self.cfg.paths.state_dir, "pids", dhash))
+        try:
+            unlink_many(must_go + pid_files)
+        except OSError as e:
+            # as before the batch: a link or limits file that will not go
+            # stops the pass, a pid file does not (those come last, so an
+            # error on one means nothing before it failed)
+            if e.filename not in pid_files:
+                raise
         # storage work batched: one transaction per GC pass, not per pod
         # (per-pod autocommit deletes fall behind at high churn)
         if self.cfg.cumask:

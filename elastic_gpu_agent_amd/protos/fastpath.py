@@ -150,6 +150,29 @@ def decode_prestart_request_digest(buf: bytes) -> dict:
     return decode_prestart_request(buf)
 
 
+# ---- hash memo: PreStart reuses the hash Allocate just computed --------------
+# For a set that is stored as runs, the runs fragment names the sorted list
+# exactly, so the native Allocate digest leaves fragment -> hash in a bounded
+# per-process memo and the PreStart digest takes it (and removes it) instead
+# of hashing the same ~200 KB again; a miss only hashes (native/wirecore.h,
+# "hash memo"). The pure-Python codecs have no memo.
+HASH_MEMO_ENTRIES = 256  # wirecore.h kMemoEntries
+
+
+def hash_memo_configure(entries: int) -> None:
+    """Entry cap of the memo; 0 turns it off and empties it."""
+    if _fastwire is not None and hasattr(_fastwire, "hash_memo_configure"):
+        _fastwire.hash_memo_configure(entries)
+
+
+def hash_memo_stats() -> dict:
+    """puts / hits / misses / evictions / entries / cap ({} without the
+    native module)."""
+    if _fastwire is not None and hasattr(_fastwire, "hash_memo_stats"):
+        return dict(_fastwire.hash_memo_stats())
+    return {}
+
+
 # ---- ID runs: how the store keeps a large device set -----------------------
 # A sorted set of mostly consecutive IDs ("0-000000" .. "0-018431") is kept as
 # [[prefix, width, start, count], ...] instead of its literal list. The rules

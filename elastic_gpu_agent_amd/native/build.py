@@ -58,7 +58,7 @@ def build_fastwire(force=False):
     src = os.path.join(HERE, "fastwire.cpp")
     ext = sysconfig.get_config_var("EXT_SUFFIX")
     out = os.path.join(PKG, f"_fastwire{ext}")
-    headers = [os.path.join(HERE, h) for h in ("wirecore.h", "bindfx.h")]
+    headers = [os.path.join(HERE, h) for h in ("wirecore.h", "idruns.h", "hashmemo.h", "bindfx.h")]
     if not force and _newer(out, src, *headers):
         return out
     _run(

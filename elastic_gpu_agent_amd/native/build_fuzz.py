@@ -96,8 +96,8 @@ def build_stride_selftest(out=None):
 
 
 def build_runs_selftest(out=None):
-    """runs_selftest.cpp: the ID-run codec of wirecore.h (digest_field_runs,
-    expand_runs), built the same way."""
+    """runs_selftest.cpp: the ID-run codec of idruns.h (RunBuilder,
+    expand_runs) under wirecore.h's digest_field_runs, built the same way."""
     out = out or os.path.join(REPO, "bin", "egpu-runs-selftest")
     return build_selftest(out, "runs_selftest.cpp")
 
@@ -118,8 +118,8 @@ def build_h2frame_selftest(out=None):
 
 
 def build_hash_memo_selftest(out=None):
-    """hash_memo_selftest.cpp: wirecore.h's HashMemo and the two digests that
-    share it, threaded case included, built the same way."""
+    """hash_memo_selftest.cpp: hashmemo.h's HashMemo and wirecore.h's two
+    digests that share it, threaded case included, built the same way."""
     out = out or os.path.join(REPO, "bin", "egpu-hash-memo-selftest")
     return build_selftest(out, "hash_memo_selftest.cpp")
 

@@ -12,48 +12,17 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <stdexcept>
 #include <string>
 #include <vector>
 
+#include "selftest_util.h"
 #include "wirecore.h"
 
 namespace {
 
-int failures = 0;
-
-#define CHECK(cond, what)                                              \
-  do {                                                                 \
-    if (!(cond)) {                                                     \
-      fprintf(stderr, "FAIL %s:%d %s (%s)\n", __FILE__, __LINE__, #cond, what); \
-      ++failures;                                                      \
-    }                                                                  \
-  } while (0)
-
-// the "hash" keeps the joined bytes so the two paths can be compared exactly
-std::string last_joined;
-void capture_digest(const void* data, size_t len, unsigned char md[32]) {
-  last_joined.assign((const char*)data, len);
-  uint64_t h = 1469598103934665603ull;
-  for (size_t i = 0; i < len; ++i) h = (h ^ ((const uint8_t*)data)[i]) * 1099511628211ull;
-  for (int i = 0; i < 32; ++i) md[i] = (unsigned char)(h >> (8 * (i & 7)));
-}
-
-void put_varint(std::string& out, uint64_t v) {
-  while (v >= 0x80) {
-    out.push_back((char)(v | 0x80));
-    v >>= 7;
-  }
-  out.push_back((char)v);
-}
-
-void put_ld(std::string& out, uint32_t field, const std::string& payload) {
-  put_varint(out, field << 3 | 2);
-  put_varint(out, payload.size());
-  out += payload;
-}
+using namespace selftest;
 
 // unknown fields of wire types 0, 1, 2, 5 and a non-LEN field 1
 std::string unknown_fields() {
@@ -65,39 +34,6 @@ std::string unknown_fields() {
   put_varint(u, 1 << 3 | 0); put_varint(u, 5);
   return u;
 }
-
-std::string encode(const std::vector<std::string>& ids, const std::string& between = "") {
-  std::string out;
-  for (auto& id : ids) {
-    put_ld(out, 1, id);
-    out += between;
-  }
-  return out;
-}
-
-std::string naive_json(const std::vector<std::string>& sorted) {
-  std::string j = "[";
-  for (size_t i = 0; i < sorted.size(); ++i) {
-    if (i) j += ",";
-    j += "\"";
-    for (unsigned char c : sorted[i]) {
-      if (c == '"' || c == '\\') { j += '\\'; j += (char)c; }
-      else if (c < 0x20) { char e[8]; snprintf(e, sizeof e, "\\u%04x", c); j += e; }
-      else j += (char)c;
-    }
-    j += "\"";
-  }
-  return j + "]";
-}
-
-struct HeapCopy {  // exact-size block: one byte past the end is poisoned
-  uint8_t* p;
-  size_t n;
-  explicit HeapCopy(const std::string& s) : p((uint8_t*)malloc(s.size() ? s.size() : 1)), n(s.size()) {
-    memcpy(p, s.data(), s.size());
-  }
-  ~HeapCopy() { free(p); }
-};
 
 // run the helper on `wire`; compare with the reference for `ids`
 void expect_ids(const std::string& wire, std::vector<std::string> ids, const char* what) {
@@ -142,7 +78,7 @@ void expect_throw(const std::string& wire, const char* what) {
 
 void run_case(const std::vector<std::string>& ids, const char* what) {
   expect_ids(encode(ids), ids, what);
-  expect_ids(encode(ids, unknown_fields()), ids, what);
+  expect_ids(encode(ids, 1, unknown_fields()), ids, what);
 }
 
 }  // namespace
@@ -208,11 +144,7 @@ int main() {
     run_case(big, "20000 sorted");
     run_case({"0-3", "0-1", "0-2"}, "3 after 20000");
     std::vector<std::string> shuffled = big;
-    uint64_t x = 88172645463325252ull;  // xorshift: deterministic shuffle
-    for (size_t i = shuffled.size() - 1; i > 0; --i) {
-      x ^= x << 13; x ^= x >> 7; x ^= x << 17;
-      std::swap(shuffled[i], shuffled[x % (i + 1)]);
-    }
+    Rng{88172645463325252ull}.shuffle(shuffled);
     run_case(shuffled, "20000 shuffled");
     run_case({"0-3", "0-1", "0-2"}, "3 after 20000 shuffled");
     expect_throw(encode(big) + std::string("\x0a\x7f", 2), "big then truncated");
@@ -266,7 +198,7 @@ int main() {
   }
 
   if (failures) {
-    fprintf(stderr, "digest selftest: %d failure(s)\n", failures);
+    fprintf(stderr, "digest selftest: %d failure(s)\n", failures.load());
     return 1;
   }
   printf("digest selftest OK\n");

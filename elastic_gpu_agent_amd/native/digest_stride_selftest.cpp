@@ -13,54 +13,20 @@
 //
 // Build + run: python -m elastic_gpu_agent_amd.native.build_fuzz --selftest
 #include <algorithm>
-#include <atomic>
 #include <cstdint>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <stdexcept>
 #include <string>
 #include <thread>
 #include <vector>
 
+#include "selftest_util.h"
 #include "wirecore.h"
 
 namespace {
 
-std::atomic<int> failures{0};  // the last case runs two threads
-
-#define CHECK(cond, what)                                              \
-  do {                                                                 \
-    if (!(cond)) {                                                     \
-      fprintf(stderr, "FAIL %s:%d %s (%s)\n", __FILE__, __LINE__, #cond, what); \
-      ++failures;                                                      \
-    }                                                                  \
-  } while (0)
-
-typedef std::vector<std::string> Ids;
-
-// the "hash" keeps the joined bytes so the two paths can be compared exactly
-thread_local std::string last_joined;
-void capture_digest(const void* data, size_t len, unsigned char md[32]) {
-  last_joined.assign((const char*)data, len);
-  uint64_t h = 1469598103934665603ull;
-  for (size_t i = 0; i < len; ++i) h = (h ^ ((const uint8_t*)data)[i]) * 1099511628211ull;
-  for (int i = 0; i < 32; ++i) md[i] = (unsigned char)(h >> (8 * (i & 7)));
-}
-
-void put_varint(std::string& out, uint64_t v) {
-  while (v >= 0x80) {
-    out.push_back((char)(v | 0x80));
-    v >>= 7;
-  }
-  out.push_back((char)v);
-}
-
-void put_ld(std::string& out, uint32_t field, const std::string& payload) {
-  put_varint(out, field << 3 | 2);
-  put_varint(out, payload.size());
-  out += payload;
-}
+using namespace selftest;
 
 // one unknown field of each kind the walker accepts: varint, fixed64,
 // length-delimited, fixed32, and a field 1 that is not length-delimited
@@ -74,12 +40,6 @@ std::vector<std::string> unknown_kinds() {
   return k;
 }
 
-std::string encode(const Ids& ids, uint32_t field = 1) {
-  std::string out;
-  for (auto& id : ids) put_ld(out, field, id);
-  return out;
-}
-
 // `extra` goes in after entry number `at` (0 = before the first)
 std::string encode_with(const Ids& ids, size_t at, const std::string& extra) {
   std::string out;
@@ -88,37 +48,6 @@ std::string encode_with(const Ids& ids, size_t at, const std::string& extra) {
     if (i < ids.size()) put_ld(out, 1, ids[i]);
   }
   return out;
-}
-
-std::string naive_json(const Ids& sorted) {
-  std::string j = "[";
-  for (size_t i = 0; i < sorted.size(); ++i) {
-    if (i) j += ",";
-    j += "\"";
-    for (unsigned char c : sorted[i]) {
-      if (c == '"' || c == '\\') { j += '\\'; j += (char)c; }
-      else if (c < 0x20) { char e[8]; snprintf(e, sizeof e, "\\u%04x", c); j += e; }
-      else j += (char)c;
-    }
-    j += "\"";
-  }
-  return j + "]";
-}
-
-struct HeapCopy {  // exact-size block: one byte past the end is poisoned
-  uint8_t* p;
-  size_t n;
-  explicit HeapCopy(const std::string& s) : p((uint8_t*)malloc(s.size() ? s.size() : 1)), n(s.size()) {
-    memcpy(p, s.data(), s.size());
-  }
-  HeapCopy(const HeapCopy&) = delete;
-  ~HeapCopy() { free(p); }
-};
-
-bool id_less(const std::string& a, const std::string& b) {  // byte-wise, unsigned
-  size_t m = std::min(a.size(), b.size());
-  int c = m ? memcmp(a.data(), b.data(), m) : 0;
-  return c ? c < 0 : a.size() < b.size();
 }
 
 // run the helper on `wire` in all four modes; compare with the reference
@@ -167,17 +96,7 @@ void expect_throw(const std::string& wire, const char* what) {
 
 void run_case(const Ids& ids, const char* what) { expect_ids(encode(ids), ids, what); }
 
-uint64_t rng_state = 88172645463325252ull;
-uint64_t rng() {  // xorshift: deterministic
-  rng_state ^= rng_state << 13;
-  rng_state ^= rng_state >> 7;
-  rng_state ^= rng_state << 17;
-  return rng_state;
-}
-
-void shuffle(Ids& v) {
-  for (size_t i = v.size(); i > 1; --i) std::swap(v[i - 1], v[rng() % i]);
-}
+Rng rng{88172645463325252ull};
 
 // n IDs of length L over `alphabet`, in random order (duplicates possible)
 Ids random_ids(size_t n, size_t L, const std::string& alphabet) {
@@ -388,14 +307,14 @@ int main() {
       }
     Ids big;
     for (int i = 0; i < 18432; ++i) { char b[16]; snprintf(b, sizeof b, "1-%06d", i); big.push_back(b); }
-    shuffle(big);
+    rng.shuffle(big);
     run_case(big, "18432 shuffled");
     // mixed lengths keep the span sort
     Ids mixed = random_ids(300, 4, kDigits);
     Ids more = random_ids(300, 5, kDigits);
     mixed.insert(mixed.end(), more.begin(), more.end());
     mixed.push_back("");
-    shuffle(mixed);
+    rng.shuffle(mixed);
     run_case(mixed, "mixed lengths shuffled");
     Ids last_differs = random_ids(300, 6, kDigits);
     last_differs.push_back("0-00000");
@@ -407,7 +326,7 @@ int main() {
   for (int shuffled = 0; shuffled < 2; ++shuffled)
     for (size_t per_range : {1, 7}) {
       Ids ids = sorted_ids(70, 4, kDigits);
-      if (shuffled) shuffle(ids);
+      if (shuffled) rng.shuffle(ids);
       std::vector<HeapCopy*> blocks;
       std::vector<wirecore::Span> ranges;
       for (size_t i = 0; i < ids.size(); i += per_range) {
@@ -451,7 +370,7 @@ int main() {
     for (int i = 0; i < 300000; ++i) { char b[16]; snprintf(b, sizeof b, "0-%06d", i); huge.push_back(b); }
     run_case(huge, "300000 sorted");
     run_case({"0-3", "0-1", "0-2"}, "3 after 300000 sorted");
-    shuffle(huge);
+    rng.shuffle(huge);
     run_case(huge, "300000 shuffled");
     wirecore::DigestScratch& sc = wirecore::digest_scratch();
     CHECK(sc.keys.capacity() * sizeof(uint64_t) <= wirecore::kScratchCap, "keys trimmed");

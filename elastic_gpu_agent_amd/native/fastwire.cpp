@@ -23,35 +23,34 @@
 #include <openssl/evp.h>
 
 #include <algorithm>
-#include <atomic>
+#include <cerrno>
 #include <cstdint>
-#include <cstring>
-#include <iterator>
-#include <list>
-#include <mutex>
 #include <stdexcept>
 #include <string>
-#include <string_view>
-#include <unordered_map>
+#include <utility>
 #include <vector>
 
 #include "bindfx.h"
+#include "wirecore.h"
 
 namespace py = pybind11;
 
 namespace {
 
-#include "wirecore.h"
-
+using wirecore::DigestOut;
+using wirecore::DigestScratch;
 using wirecore::Reader;
-using wirecore::field1_spans;
+using wirecore::ScratchGuard;
+using wirecore::Span;
+using wirecore::span_less;
+using wirecore::spans_of;
 
 py::list decode_string_list(py::bytes data) {
   char* buf;
   Py_ssize_t len;
   PyBytes_AsStringAndSize(data.ptr(), &buf, &len);
-  std::vector<std::pair<const uint8_t*, size_t>> spans;
-  field1_spans((const uint8_t*)buf, (const uint8_t*)buf + len, spans);
+  std::vector<Span> spans;
+  spans_of((const uint8_t*)buf, (const uint8_t*)buf + len, 1, spans);
   py::list out;
   for (auto& s : spans)
     out.append(py::str((const char*)s.first, s.second));
@@ -62,12 +61,12 @@ py::list decode_nested_string_lists(py::bytes data) {
   char* buf;
   Py_ssize_t len;
   PyBytes_AsStringAndSize(data.ptr(), &buf, &len);
-  std::vector<std::pair<const uint8_t*, size_t>> outer;
-  field1_spans((const uint8_t*)buf, (const uint8_t*)buf + len, outer);
+  std::vector<Span> outer;
+  spans_of((const uint8_t*)buf, (const uint8_t*)buf + len, 1, outer);
   py::list out;
   for (auto& o : outer) {
-    std::vector<std::pair<const uint8_t*, size_t>> inner;
-    field1_spans(o.first, o.first + o.second, inner);
+    std::vector<Span> inner;
+    spans_of(o.first, o.first + o.second, 1, inner);
     py::list ids;
     for (auto& s : inner)
       ids.append(py::str((const char*)s.first, s.second));
@@ -84,6 +83,15 @@ void put_varint(std::string& out, uint64_t v) {
   out.push_back((char)v);
 }
 
+size_t varint_size(uint64_t v) {
+  size_t n = 1;
+  while (v >= 0x80) {
+    v >>= 7;
+    ++n;
+  }
+  return n;
+}
+
 py::bytes encode_device_list(const std::vector<std::string>& ids, py::bytes suffix_b) {
   char* sbuf;
   Py_ssize_t slen;
@@ -92,14 +100,6 @@ py::bytes encode_device_list(const std::vector<std::string>& ids, py::bytes suff
   size_t est = 0;
   for (auto& id : ids) est += id.size() + slen + 10;
   out.reserve(est);
-  auto varint_size = [](uint64_t v) {
-    size_t n = 1;
-    while (v >= 0x80) {
-      v >>= 7;
-      ++n;
-    }
-    return n;
-  };
   for (auto& id : ids) {
     // device submessage: field 1 (ID string) + suffix
     size_t body = 1 + varint_size(id.size()) + id.size() + slen;
@@ -111,15 +111,6 @@ py::bytes encode_device_list(const std::vector<std::string>& ids, py::bytes suff
     out.append(sbuf, slen);
   }
   return py::bytes(out);
-}
-
-size_t varint_size(uint64_t v) {
-  size_t n = 1;
-  while (v >= 0x80) {
-    v >>= 7;
-    ++n;
-  }
-  return n;
 }
 
 // repeated string field 1 (PreStartContainerRequest / inner container bodies)
@@ -166,20 +157,15 @@ void sha256_evp(const void* data, size_t len, unsigned char md[32]) {
   EVP_Digest(data, len, md, &mdlen, EVP_sha256(), nullptr);
 }
 
-using wirecore::DigestOut;
-using wirecore::DigestScratch;
-using wirecore::ScratchGuard;
-using wirecore::Span;
-
 // fragment -> hash of the large sets Allocate has digested and PreStart has
-// not yet taken (wirecore.h, "hash memo"); one per process
+// not yet taken (hashmemo.h); one per process
 wirecore::HashMemo g_hash_memo;
 
 std::vector<std::pair<std::string, size_t>> digest_raw(const uint8_t* p, size_t len) {
   // container requests are few (one per container); only the per-container
   // ID walk is hot
   std::vector<Span> outer;
-  field1_spans(p, p + len, outer);
+  spans_of(p, p + len, 1, outer);
   std::vector<std::pair<std::string, size_t>> result;
   result.reserve(outer.size());
   DigestScratch& sc = wirecore::digest_scratch();
@@ -254,9 +240,9 @@ py::tuple decode_prestart_digest2(py::bytes data) {
 // its runs fragment ([[prefix, width, start, count], ...], is_runs = True)
 // and its literal list is never built: the store keeps the runs, and
 // expand_runs rebuilds the list for the few readers that want it. Sets that
-// do not qualify (wirecore.h, "ID runs") come back exactly as from v2. A set
-// that qualifies and was digested by Allocate just before takes its hash
-// from the memo instead of hashing the same bytes again.
+// do not qualify (idruns.h) come back exactly as from v2. A set that qualifies
+// and was digested by Allocate just before takes its hash from the memo
+// (hashmemo.h) instead of hashing the same bytes again.
 py::tuple decode_prestart_digest3(py::bytes data) {
   char* buf;
   Py_ssize_t len;
@@ -267,8 +253,8 @@ py::tuple decode_prestart_digest3(py::bytes data) {
   bool is_runs = false;
   {
     py::gil_scoped_release rel;
-    d = wirecore::digest_field_runs_take(sc, (const uint8_t*)buf, (size_t)len, 1,
-                                         sha256_evp, &is_runs, &g_hash_memo);
+    d = wirecore::digest_field_runs(sc, (const uint8_t*)buf, (size_t)len, 1, sha256_evp,
+                                    &is_runs, &g_hash_memo);
   }
   return py::make_tuple(py::str(d.hex, 8), (long long)d.count,
                         py::bytes(sc.json.data(), d.json_len), is_runs);
@@ -363,50 +349,33 @@ py::list podresources_digest(py::bytes data) {
   {
     py::gil_scoped_release rel;
     DigestScratch& sc = wirecore::digest_scratch();
-    auto span_fields = [](const uint8_t* p, const uint8_t* end, uint32_t want,
-                          std::vector<std::pair<const uint8_t*, size_t>>& out) {
-      Reader r{p, end};
-      while (!r.done()) {
-        uint64_t tag = r.varint();
-        uint32_t field = tag >> 3, wire = tag & 7;
-        if (field == want && wire == 2) {
-          uint64_t n = r.varint();
-          if (n > (uint64_t)(r.end - r.p)) throw std::runtime_error("truncated");
-          out.emplace_back(r.p, (size_t)n);
-          r.p += n;
-        } else {
-          r.skip(wire);
-        }
-      }
-    };
-    std::vector<std::pair<const uint8_t*, size_t>> pods;
-    span_fields((const uint8_t*)buf, (const uint8_t*)buf + len, 1, pods);
+    std::vector<Span> pods;
+    spans_of((const uint8_t*)buf, (const uint8_t*)buf + len, 1, pods);
     for (auto& pspan : pods) {
-      std::vector<std::pair<const uint8_t*, size_t>> f;
+      std::vector<Span> f;
       std::string pod_name, pod_ns;
       f.clear();
-      span_fields(pspan.first, pspan.first + pspan.second, 1, f);
+      spans_of(pspan.first, pspan.first + pspan.second, 1, f);
       if (!f.empty()) pod_name.assign((const char*)f[0].first, f[0].second);
       f.clear();
-      span_fields(pspan.first, pspan.first + pspan.second, 2, f);
+      spans_of(pspan.first, pspan.first + pspan.second, 2, f);
       if (!f.empty()) pod_ns.assign((const char*)f[0].first, f[0].second);
-      std::vector<std::pair<const uint8_t*, size_t>> containers;
-      span_fields(pspan.first, pspan.first + pspan.second, 3, containers);
+      std::vector<Span> containers;
+      spans_of(pspan.first, pspan.first + pspan.second, 3, containers);
       for (auto& cspan : containers) {
         f.clear();
-        span_fields(cspan.first, cspan.first + cspan.second, 1, f);
+        spans_of(cspan.first, cspan.first + cspan.second, 1, f);
         std::string cname;
         if (!f.empty()) cname.assign((const char*)f[0].first, f[0].second);
-        std::vector<std::pair<const uint8_t*, size_t>> devs;
-        span_fields(cspan.first, cspan.first + cspan.second, 2, devs);
+        std::vector<Span> devs;
+        spans_of(cspan.first, cspan.first + cspan.second, 2, devs);
         // group the ContainerDevices entries per resource_name (a container
         // may list a resource in one entry pre-1.21 or one entry per ID
         // after); the digest walks each group's entries as one ID set
-        std::vector<std::pair<std::string,
-                              std::vector<std::pair<const uint8_t*, size_t>>>> groups;
+        std::vector<std::pair<std::string, std::vector<Span>>> groups;
         for (auto& dspan : devs) {
           f.clear();
-          span_fields(dspan.first, dspan.first + dspan.second, 1, f);
+          spans_of(dspan.first, dspan.first + dspan.second, 1, f);
           std::string res;
           if (!f.empty()) res.assign((const char*)f[0].first, f[0].second);
           bool found = false;
@@ -417,8 +386,7 @@ py::list podresources_digest(py::bytes data) {
               break;
             }
           if (!found)
-            groups.emplace_back(
-                res, std::vector<std::pair<const uint8_t*, size_t>>{dspan});
+            groups.emplace_back(res, std::vector<Span>{dspan});
         }
         for (auto& g : groups) {
           auto& ranges = g.second;
@@ -450,8 +418,8 @@ py::list podresources_digest(py::bytes data) {
 // materializing Python strings.
 
 struct PreferredContainer {
-  std::vector<std::pair<const uint8_t*, size_t>> available;
-  std::vector<std::pair<const uint8_t*, size_t>> must_include;
+  std::vector<Span> available;
+  std::vector<Span> must_include;
   long long size = 0;
 };
 
@@ -469,8 +437,8 @@ long long gpu_prefix(const uint8_t* p, size_t n) {
 
 void parse_preferred(const uint8_t* p, size_t len,
                      std::vector<PreferredContainer>& out) {
-  std::vector<std::pair<const uint8_t*, size_t>> outer;
-  field1_spans(p, p + len, outer);
+  std::vector<Span> outer;
+  spans_of(p, p + len, 1, outer);
   out.resize(outer.size());
   for (size_t i = 0; i < outer.size(); ++i) {
     Reader r{outer[i].first, outer[i].first + outer[i].second};
@@ -544,15 +512,11 @@ py::bytes preferred_extract(py::bytes data, size_t index, long long gpu, size_t 
     std::vector<PreferredContainer> containers;
     parse_preferred((const uint8_t*)buf, (size_t)len, containers);
     if (index >= containers.size()) throw std::runtime_error("bad container index");
-    std::vector<std::pair<const uint8_t*, size_t>> group;
+    std::vector<Span> group;
     for (auto& s : containers[index].available)
       if (gpu_prefix(s.first, s.second) == gpu) group.push_back(s);
-    auto cmp = [](const std::pair<const uint8_t*, size_t>& a,
-                  const std::pair<const uint8_t*, size_t>& b) {
-      int c = memcmp(a.first, b.first, std::min(a.second, b.second));
-      if (c) return c < 0;
-      return a.second < b.second;
-    };
+    // a lambda, not the function's address: the sorts inline the compare
+    auto cmp = [](const Span& a, const Span& b) { return span_less(a, b); };
     if (n < group.size()) {
       std::nth_element(group.begin(), group.begin() + n, group.end(), cmp);
       group.resize(n);

@@ -6,16 +6,16 @@
 // corpus exercising every parser:
 //   0: HPACK header-block decode (h2core.h — the code in _etransport)
 //   1: Huffman string decode
-//   2: protobuf wire walk (wirecore.h field1_spans — the code in _fastwire)
+//   2: protobuf wire walk (wirecore.h spans_of — the code in _fastwire)
 //   3: AllocateRequest digest (outer field1 → wirecore.h digest_field per
 //      container: the fused walk/check/join/hash helper behind _fastwire),
 //      and the same set through digest_field_runs: where it comes back as ID
 //      runs, expanding them must give the literal list fragment; and once
-//      more through the Allocate and PreStart digests that share a hash memo:
-//      digest with memo == digest without
+//      more through the Allocate and PreStart digests with a hash memo
+//      (hashmemo.h): digest with memo == digest without
 //   4: minijson parse (OCI config/state parsing in egpu-hook); the same
 //      bytes, read as a 16-bit ID count and a runs fragment, through
-//      wirecore.h expand_runs (what the store reads back)
+//      idruns.h parse_runs / write_runs (what the store reads back)
 //   5: devfilter OCI device-rule extraction + eBPF program build
 //
 // Build + run: python -m elastic_gpu_agent_amd.native.build_fuzz
@@ -28,6 +28,8 @@
 
 #include "h2core.h"
 #include "minijson.h"
+#define SELFTEST_UTIL_NO_CHECKS  // the hash and the encoders only
+#include "selftest_util.h"
 #include "wirecore.h"
 
 // devfilter's parser + program builder (no kernel interaction in build)
@@ -47,9 +49,9 @@ void fuzz_huffman(const uint8_t* data, size_t size) {
 }
 
 void fuzz_wire(const uint8_t* data, size_t size) {
-  std::vector<std::pair<const uint8_t*, size_t>> spans;
+  std::vector<wirecore::Span> spans;
   try {
-    wirecore::field1_spans(data, data + size, spans);
+    wirecore::spans_of(data, data + size, 1, spans);
   } catch (const std::runtime_error&) {
   }
   // every reported span must stay inside the input
@@ -58,22 +60,17 @@ void fuzz_wire(const uint8_t* data, size_t size) {
   }
 }
 
-// stand-in for sha256: the harness links no crypto library. It reads every
-// joined byte, so ASan sees any join that ran past its buffer.
-void sum_digest(const void* data, size_t len, unsigned char md[32]) {
-  uint64_t h = 1469598103934665603ull;
-  const uint8_t* p = (const uint8_t*)data;
-  for (size_t i = 0; i < len; ++i) h = (h ^ p[i]) * 1099511628211ull;
-  for (int i = 0; i < 32; ++i) md[i] = (unsigned char)(h >> (8 * (i & 7)));
-}
+// the stand-in for sha256 reads every joined byte, so ASan sees any join
+// that ran past its buffer
+constexpr wirecore::Sha256Fn sum_digest = selftest::fnv_digest;
 
 // the shipped digest: outer field1 -> per container the fused walk / order
 // check / join / hash helper, JSON fragment and sorted spans included
 void fuzz_wire_nested(const uint8_t* data, size_t size) {
-  std::vector<std::pair<const uint8_t*, size_t>> outer;
+  std::vector<wirecore::Span> outer;
   wirecore::DigestScratch& sc = wirecore::digest_scratch();
   try {
-    wirecore::field1_spans(data, data + size, outer);
+    wirecore::spans_of(data, data + size, 1, outer);
     for (auto& o : outer) {
       // without spans an unsorted fixed-width set takes the radix fallback,
       // with spans the span sort: hash and fragment must not differ
@@ -103,7 +100,7 @@ void fuzz_wire_nested(const uint8_t* data, size_t size) {
       const size_t count = d.count;
       bool is_runs = false;
       wirecore::DigestOut r =
-          wirecore::digest_field_runs(sc, o.first, o.second, 1, sum_digest, &is_runs);
+          wirecore::digest_field_runs(sc, o.first, o.second, 1, sum_digest, &is_runs, nullptr);
       if (hex_no_spans != r.hex || r.count != count) __builtin_trap();
       if (r.json_len > sc.json.size()) __builtin_trap();
       if (is_runs) {
@@ -123,7 +120,7 @@ void fuzz_wire_nested(const uint8_t* data, size_t size) {
       if (hex_no_spans != a.hex || a.count != count) __builtin_trap();
       for (int pass = 0; pass < 2; ++pass) {
         bool memo_runs = false;
-        wirecore::DigestOut t = wirecore::digest_field_runs_take(
+        wirecore::DigestOut t = wirecore::digest_field_runs(
             sc, o.first, o.second, 1, sum_digest, &memo_runs, &memo);
         if (hex_no_spans != t.hex || t.count != count || memo_runs != is_runs)
           __builtin_trap();
@@ -156,7 +153,7 @@ void fuzz_runs_expand(const uint8_t* data, size_t size) {
   const uint64_t count = data[0] | (uint64_t)data[1] << 8;
   try {
     wirecore::RunsPlan plan = wirecore::parse_runs((const char*)data + 2, size - 2, count);
-    if (plan.total > wirecore::kScratchCap) __builtin_trap();
+    if (plan.total > wirecore::kRunsMaxExpanded) __builtin_trap();
     char* out = (char*)malloc(plan.total);
     wirecore::write_runs(plan, out);
     if (out[0] != '[' || out[plan.total - 1] != ']') __builtin_trap();

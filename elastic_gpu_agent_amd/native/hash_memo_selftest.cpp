@@ -1,5 +1,5 @@
-// Stand-alone check of the hash memo in wirecore.h (HashMemo,
-// digest_field_put, digest_field_runs_take), meant to be built with
+// Stand-alone check of the hash memo in hashmemo.h and wirecore.h (HashMemo,
+// digest_field_put, digest_field_runs), meant to be built with
 // -fsanitize=address,undefined and run directly (the pybind modules
 // themselves are never run under a sanitizer). Companion of runs_selftest.cpp.
 //
@@ -22,55 +22,22 @@
 #include <thread>
 #include <vector>
 
+#include "selftest_util.h"
 #include "wirecore.h"
 
 namespace {
 
-std::atomic<int> failures{0};
-
-#define CHECK(cond, what)                                                          \
-  do {                                                                             \
-    if (!(cond)) {                                                                 \
-      fprintf(stderr, "FAIL %s:%d %s (%s)\n", __FILE__, __LINE__, #cond, what);    \
-      ++failures;                                                                  \
-    }                                                                              \
-  } while (0)
-
-typedef std::vector<std::string> Ids;
+using selftest::HeapCopy;
+using selftest::Ids;
+using selftest::encode;
+using selftest::failures;
 
 // stand-in for sha256 (no crypto library here); counts its calls per thread
 thread_local int sha_calls = 0;
 void fnv_digest(const void* data, size_t len, unsigned char md[32]) {
   ++sha_calls;
-  uint64_t h = 1469598103934665603ull;
-  for (size_t i = 0; i < len; ++i) h = (h ^ ((const uint8_t*)data)[i]) * 1099511628211ull;
-  for (int i = 0; i < 32; ++i) md[i] = (unsigned char)(h >> (8 * (i & 7)));
+  selftest::fnv_digest(data, len, md);
 }
-
-std::string encode(const Ids& ids) {
-  std::string out;
-  for (auto& id : ids) {
-    out.push_back(0x0A);
-    size_t v = id.size();
-    while (v >= 0x80) {
-      out.push_back((char)(v | 0x80));
-      v >>= 7;
-    }
-    out.push_back((char)v);
-    out += id;
-  }
-  return out;
-}
-
-struct HeapCopy {  // exact-size block: one byte past the end is poisoned
-  uint8_t* p;
-  size_t n;
-  explicit HeapCopy(const std::string& s) : p((uint8_t*)malloc(s.size() ? s.size() : 1)), n(s.size()) {
-    memcpy(p, s.data(), s.size());
-  }
-  HeapCopy(const HeapCopy&) = delete;
-  ~HeapCopy() { free(p); }
-};
 
 Ids id_range(int gpu, size_t start, size_t n, int width = 6) {
   Ids ids;
@@ -112,8 +79,7 @@ Result prestart(const Ids& ids, wirecore::HashMemo* memo) {
   wirecore::ScratchGuard guard(sc);
   bool is_runs = false;
   wirecore::DigestOut d =
-      memo ? wirecore::digest_field_runs_take(sc, in.p, in.n, 1, fnv_digest, &is_runs, memo)
-           : wirecore::digest_field_runs(sc, in.p, in.n, 1, fnv_digest, &is_runs);
+      wirecore::digest_field_runs(sc, in.p, in.n, 1, fnv_digest, &is_runs, memo);
   return Result{d.hex, std::string(sc.json.data(), d.json_len), d.count, is_runs};
 }
 
@@ -246,7 +212,7 @@ void test_pairs() {
   threw = false;
   try {
     wirecore::ScratchGuard guard(sc);
-    wirecore::digest_field_runs_take(sc, in.p, in.n, 1, fnv_digest, &is_runs, &memo);
+    wirecore::digest_field_runs(sc, in.p, in.n, 1, fnv_digest, &is_runs, &memo);
   } catch (const std::runtime_error&) {
     threw = true;
   }

@@ -1,4 +1,4 @@
-// Stand-alone check of the ID-run codec in wirecore.h (RunBuilder,
+// Stand-alone check of the ID-run codec in idruns.h and wirecore.h (RunBuilder,
 // digest_field_runs, parse_runs / write_runs / expand_runs), meant to be built
 // with -fsanitize=address,undefined and run directly (the pybind modules
 // themselves are never run under a sanitizer). Companion of
@@ -22,79 +22,12 @@
 #include <string>
 #include <vector>
 
+#include "selftest_util.h"
 #include "wirecore.h"
 
 namespace {
 
-int failures = 0;
-
-#define CHECK(cond, what)                                                          \
-  do {                                                                             \
-    if (!(cond)) {                                                                 \
-      fprintf(stderr, "FAIL %s:%d %s (%s)\n", __FILE__, __LINE__, #cond, what);    \
-      ++failures;                                                                  \
-    }                                                                              \
-  } while (0)
-
-typedef std::vector<std::string> Ids;
-
-std::string last_joined;
-void capture_digest(const void* data, size_t len, unsigned char md[32]) {
-  last_joined.assign((const char*)data, len);
-  uint64_t h = 1469598103934665603ull;
-  for (size_t i = 0; i < len; ++i) h = (h ^ ((const uint8_t*)data)[i]) * 1099511628211ull;
-  for (int i = 0; i < 32; ++i) md[i] = (unsigned char)(h >> (8 * (i & 7)));
-}
-
-void put_varint(std::string& out, uint64_t v) {
-  while (v >= 0x80) {
-    out.push_back((char)(v | 0x80));
-    v >>= 7;
-  }
-  out.push_back((char)v);
-}
-
-std::string encode(const Ids& ids) {
-  std::string out;
-  for (auto& id : ids) {
-    out.push_back(0x0A);
-    put_varint(out, id.size());
-    out += id;
-  }
-  return out;
-}
-
-struct HeapCopy {  // exact-size block: one byte past the end is poisoned
-  uint8_t* p;
-  size_t n;
-  explicit HeapCopy(const std::string& s) : p((uint8_t*)malloc(s.size() ? s.size() : 1)), n(s.size()) {
-    memcpy(p, s.data(), s.size());
-  }
-  HeapCopy(const HeapCopy&) = delete;
-  ~HeapCopy() { free(p); }
-};
-
-bool id_less(const std::string& a, const std::string& b) {  // byte-wise, unsigned
-  size_t m = std::min(a.size(), b.size());
-  int c = m ? memcmp(a.data(), b.data(), m) : 0;
-  if (c) return c < 0;
-  return a.size() < b.size();
-}
-
-std::string naive_json(const Ids& sorted) {
-  std::string j = "[";
-  for (size_t i = 0; i < sorted.size(); ++i) {
-    if (i) j += ",";
-    j += "\"";
-    for (unsigned char c : sorted[i]) {
-      if (c == '"' || c == '\\') { j += '\\'; j += (char)c; }
-      else if (c < 0x20) { char e[8]; snprintf(e, sizeof e, "\\u%04x", c); j += e; }
-      else j += (char)c;
-    }
-    j += "\"";
-  }
-  return j + "]";
-}
+using namespace selftest;
 
 // the format, from its description: "" where the set keeps its literal list
 std::string naive_runs(const Ids& sorted) {
@@ -127,17 +60,7 @@ std::string naive_runs(const Ids& sorted) {
   return j + "]";
 }
 
-uint64_t rng_state = 0x9E3779B97F4A7C15ull;
-uint64_t rnd() {
-  rng_state ^= rng_state << 13;
-  rng_state ^= rng_state >> 7;
-  rng_state ^= rng_state << 17;
-  return rng_state;
-}
-
-void shuffle(Ids& v) {
-  for (size_t i = v.size(); i > 1; --i) std::swap(v[i - 1], v[rnd() % i]);
-}
+Rng rnd{0x9E3779B97F4A7C15ull};
 
 void check_set(Ids ids, const char* what) {
   Ids sorted = ids;
@@ -145,7 +68,7 @@ void check_set(Ids ids, const char* what) {
   const std::string want_list = naive_json(sorted);
   const std::string want_runs = naive_runs(sorted);
   Ids shuffled = ids;
-  shuffle(shuffled);
+  rnd.shuffle(shuffled);
   const Ids* orders[2] = {&sorted, &shuffled};
   wirecore::DigestScratch& sc = wirecore::digest_scratch();
   for (int o = 0; o < 2; ++o) {
@@ -162,7 +85,7 @@ void check_set(Ids ids, const char* what) {
     bool is_runs = false;
     last_joined.clear();
     wirecore::DigestOut d =
-        wirecore::digest_field_runs(sc, in.p, in.n, 1, capture_digest, &is_runs);
+        wirecore::digest_field_runs(sc, in.p, in.n, 1, capture_digest, &is_runs, nullptr);
     CHECK(ref_hex == d.hex, what);
     CHECK(ref_joined == last_joined, what);
     CHECK(d.count == sorted.size(), what);
@@ -248,6 +171,46 @@ int main() {
   check_set(cat(cat(seq("0-%06llu", 0, 1500), seq("10-%06llu", 0, 1500)),
                 seq("gpu-long-prefix-%08llu", 0, 1500)), "mixed lengths");
   check_set(seq("a:b:%05llu", 0, 1500), "colons in the prefix");
+  // every stride length, sorted (the run's one or two words) and shuffled
+  // (the radix output up to L = 8): consecutive IDs whose tails cross a
+  // one-carry boundary (x9 -> y0) and a two-carry one (x99 -> y00). The
+  // exception is L = 1: ten IDs are far below the 3 * kRunsMinIds wire bytes
+  // at which digest_field_runs attaches a RunBuilder, so there only the
+  // digest and the RunBuilder alone are compared, not `successor`.
+  check_set(seq("%llu", 0, 10), "sweep L = 1");
+  for (int L = 2; L <= 16; ++L) {
+    Ids v;
+    char b[32];
+    if (L >= 4) {
+      // 1500 IDs from 950: past 999 -> 1000; a letter in front from L = 5
+      for (unsigned long long i = 950; i < 950 + 1500; ++i) {
+        if (L == 4) snprintf(b, sizeof b, "%04llu", i);
+        else snprintf(b, sizeof b, "a%0*llu", L - 1, i);
+        v.push_back(b);
+      }
+    } else {
+      // two or three bytes: every all-digit ID (09 -> 10, 099 -> 100), then
+      // blocks with another byte in front; from the last ID of a block (99,
+      // a9) no carry leads to the next. L = 3 takes letters up to 1500 IDs.
+      // L = 2 takes every printable byte json.dumps leaves alone: 920 IDs,
+      // too few to be stored as runs, but past the 768 entries from which
+      // the walk runs with a RunBuilder and evaluates `successor`.
+      for (int i = 0; i < (L == 2 ? 100 : 1000); ++i) {
+        snprintf(b, sizeof b, "%0*d", L, i);
+        v.push_back(b);
+      }
+      for (int c = L == 2 ? '!' : 'a'; c <= (L == 2 ? '~' : 'z') && v.size() < 1500; ++c) {
+        if ((c >= '0' && c <= '9') || c == '"' || c == '\\') continue;
+        for (int i = 0; i < (L == 2 ? 10 : 100); ++i) {
+          snprintf(b, sizeof b, "%c%0*d", c, L - 1, i);
+          v.push_back(b);
+        }
+      }
+      if (L == 2) CHECK(encode(v).size() >= 3 * wirecore::kRunsMinIds, "sweep L = 2 is walked with runs");
+    }
+    snprintf(b, sizeof b, "sweep L = %d", L);
+    check_set(v, b);
+  }
   // not run-encodable somewhere in a large set
   check_set(cat(seq("0-%06llu", 0, 2000), Ids{"0-abc"}), "no digits");
   check_set(cat(seq("0-%06llu", 0, 2000), Ids{"0-\"1"}), "quote");
@@ -299,7 +262,7 @@ int main() {
   expect_reject("[[\"0-\",06,0,5]]", 5);
   expect_reject("[[\"0\\u002d\",6,0,5]]", 5);
   expect_reject("[[\"0-\",6,0,5]]x", 5);
-  expect_reject("[[\"0-\",18,0,600000]]", 600000);  // over kScratchCap
+  expect_reject("[[\"0-\",18,0,600000]]", 600000);  // over kRunsMaxExpanded
   expect_reject("[[\"0-\",18,0,999999999999999999]]", 999999999999999999ull);
   expect_reject("[[\"0-\",6,0,99999999999999999999]]", 5);
   expect_reject("[[\"0-\",6,0,18446744073709551615]]", 18446744073709551615ull);
@@ -318,7 +281,7 @@ int main() {
         "whitespace");
 
   if (failures) {
-    fprintf(stderr, "%d check(s) failed\n", failures);
+    fprintf(stderr, "%d check(s) failed\n", failures.load());
     return 1;
   }
   printf("runs selftest OK\n");

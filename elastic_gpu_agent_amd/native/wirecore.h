@@ -1,23 +1,27 @@
-// wirecore.h — protobuf wire-walking core shared by _fastwire and the
-// standalone fuzz targets. Header-only; extracted verbatim from
-// fastwire.cpp so fuzzing covers exactly the shipped parser.
+// wirecore.h — the protobuf wire reader and the fused device-set digest of
+// _fastwire: Reader and spans_of walk LEN fields, DigestWriter / digest_ranges
+// hash (and print) an ID set in one pass, and digest_field, digest_field_put
+// and digest_field_runs are the entry points of the Allocate and PreStart
+// handlers. Header-only, standard library only, shared with the fuzz targets
+// and the sanitizer self-tests so they run exactly the shipped code. The
+// ID-run codec (idruns.h) and the hash memo (hashmemo.h) come with it.
 #pragma once
 
 #include <algorithm>
-#include <atomic>
+#include <cstddef>
 #include <cstdint>
 #include <cstring>
-#include <iterator>
-#include <list>
-#include <mutex>
 #include <stdexcept>
 #include <string>
-#include <string_view>
-#include <unordered_map>
 #include <utility>
 #include <vector>
 
+#include "hashmemo.h"
+#include "idruns.h"
+
 namespace wirecore {
+
+using Span = std::pair<const uint8_t*, size_t>;
 
 struct Reader {
   const uint8_t* p;
@@ -67,28 +71,9 @@ struct Reader {
   }
 };
 
-// collect every field-1 LEN payload within [p, end)
-inline void field1_spans(const uint8_t* p, const uint8_t* end,
-                  std::vector<std::pair<const uint8_t*, size_t>>& out) {
-  Reader r{p, end};
-  while (!r.done()) {
-    uint64_t tag = r.varint();
-    uint32_t field = tag >> 3, wire = tag & 7;
-    if (field == 1 && wire == 2) {
-      uint64_t n = r.varint();
-      if (n > (uint64_t)(r.end - r.p)) throw std::runtime_error("truncated");
-      out.emplace_back(r.p, (size_t)n);
-      r.p += n;
-    } else {
-      r.skip(wire);
-    }
-  }
-}
-
-
-// collect every field-N LEN payload within [p, end)
-inline void spanN(const uint8_t* p, const uint8_t* end, uint32_t want,
-                  std::vector<std::pair<const uint8_t*, size_t>>& out) {
+// collect every field-`want` LEN payload within [p, end)
+inline void spans_of(const uint8_t* p, const uint8_t* end, uint32_t want,
+                     std::vector<Span>& out) {
   Reader r{p, end};
   while (!r.done()) {
     uint64_t tag = r.varint();
@@ -144,7 +129,6 @@ inline void spanN(const uint8_t* p, const uint8_t* end, uint32_t want,
 // The caller supplies the hash (sha256 over a buffer → 32 bytes) so this
 // header keeps no dependency beyond the standard library.
 
-using Span = std::pair<const uint8_t*, size_t>;
 using Sha256Fn = void (*)(const void* data, size_t len, unsigned char md[32]);
 
 constexpr size_t kScratchCap = 4u << 20;  // bytes retained per buffer
@@ -207,154 +191,106 @@ inline bool span_less(const Span& a, const Span& b) {
   return a.second < b.second;
 }
 
-// ---- ID runs ----------------------------------------------------------------
-// The IDs of a resource are "<gpu>-<zero-padded index>", and kubelet hands out
-// mostly consecutive ones, so a large sorted set is a handful of runs. The
-// store keeps such a set as [[prefix, width, start, count], ...] (200 KB of
-// literal list become ~20 bytes); the literal list stays the exchange format
-// and expand_runs rebuilds it byte for byte.
-//
-// An ID is run-encodable when it ends in a maximal run of 1..18 ASCII digits
-// (so the value fits a uint64) and holds no byte json.dumps would escape
-// ('"', '\\', < 0x20, >= 0x80). Over the sorted set an ID with the prefix and
-// width of its predecessor and value == previous + 1 extends the run; anything
-// else (a duplicate, 9 -> 10, another prefix) starts one. A set is stored as
-// runs only when every ID is run-encodable, it has >= kRunsMinIds IDs and at
-// most count / kRunsPerIds runs: small sets keep their literal bytes and a
-// fragmented set never grows.
+// ---- fixed-stride keys ---------------------------------------------------------
+// An ID of the run's one length L as the words DigestWriter::run and put_keys
+// compare, test and store. Both key types offer the same operations: load (an
+// entry inside [.., end)), load_exact (exactly L bytes), less (byte-wise
+// order), successor (b is a plus one in the last digit, or plus one with one
+// carry, x9 -> y0, the digit before it below 9: the IDs RunBuilder only
+// counts), needs_escape (a byte json.dumps escapes) and store (whole words,
+// up to kWordSlack - 1 bytes past the ID).
 
-constexpr size_t kRunsMinIds = 1024;
-constexpr size_t kRunsPerIds = 8;
-constexpr size_t kRunsMaxWidth = 18;
+// 1 <= L <= 8: one left-aligned big-endian word
+struct NarrowKey {
+  struct Val {
+    uint64_t raw;  // as loaded; the bytes past the ID are whatever followed it
+    uint64_t key;  // big-endian, the bytes past the ID zero
+  };
+  size_t L;
+  int sh;  // shift of the last byte
+  uint64_t mask;
+  uint64_t pad;  // the bytes past the ID must not look like bytes to escape
 
-struct IdRun {
-  size_t prefix_off, prefix_len;  // into RunBuilder::prefixes
-  unsigned width;
-  uint64_t start, count;
+  explicit NarrowKey(size_t len)
+      : L(len), sh(64 - 8 * (int)len), mask(~0ull << sh),
+        pad(~mask & 0x3030303030303030ull) {}
+
+  static Val of(uint64_t key) { return Val{word_to_be(key), key}; }
+
+  // a whole-word load where 8 bytes remain in the range, L bytes otherwise
+  // (the last entries of a range)
+  Val load(const uint8_t* id, const uint8_t* end) const {
+    uint64_t raw = 0;
+    if ((size_t)(end - id) >= 8)
+      memcpy(&raw, id, 8);
+    else
+      memcpy(&raw, id, L);
+    return Val{raw, word_to_be(raw) & mask};
+  }
+  Val load_exact(const uint8_t* id) const { return of(be_key_bytes(id, L)); }
+
+  bool less(const Val& a, const Val& b) const { return a.key < b.key; }
+  // on the right-aligned words: the last digit is the low byte, and x9 -> y0
+  // adds 256 - 9 (at L = 1 the byte before the last is 0, never a digit)
+  bool successor(const Val& a, const Val& b) const {
+    const uint64_t t = a.key >> sh;
+    const uint64_t d = (b.key >> sh) - t;
+    const unsigned d0 = (unsigned)(t & 0xFF) - '0';
+    return (d == 1 && d0 < 9) ||
+           (d == 247 && d0 == 9 && (unsigned)(((t >> 8) & 0xFF) - '0') < 9);
+  }
+  bool needs_escape(const Val& v) const { return word_needs_escape(v.key | pad); }
+  void store(char* out, const Val& v) const { memcpy(out, &v.raw, 8); }
 };
 
-// Fed the sorted IDs one by one. The expected successor is kept as text, so
-// an ID that extends the run costs one compare and an ASCII increment. The
-// digest's word-at-a-time loops see "previous ID + 1 in the last digit" and
-// "previous ID + 1 with one carry (x9 -> y0)" on the words they already hold
-// and only report how many such IDs went by and the last of them (extend), so
-// 99 of 100 consecutive IDs never reach add.
-struct RunBuilder {
-  std::vector<IdRun> runs;
-  std::string prefixes;
-  std::string next;  // the ID that would extend the last run
-  bool has_next = false;
-  bool ok = true;    // every ID so far is run-encodable, runs within max_runs
-  size_t n = 0;
-  size_t max_runs = 0;
+// 9 <= L <= kMaxStride: two overlapping words, the first 8 bytes and the last 8
+struct WideKey {
+  struct Val {
+    uint64_t rh, rl;  // as loaded
+    uint64_t kh, kl;  // big-endian
+  };
+  size_t L, off;
 
-  void reset(size_t run_cap) {
-    runs.clear();
-    prefixes.clear();
-    has_next = false;
-    ok = true;
-    n = 0;
-    max_runs = run_cap;
+  explicit WideKey(size_t len) : L(len), off(len - 8) {}
+
+  // both words lie inside the ID
+  Val load_exact(const uint8_t* id) const {
+    Val v;
+    memcpy(&v.rh, id, 8);
+    memcpy(&v.rl, id + off, 8);
+    v.kh = word_to_be(v.rh);
+    v.kl = word_to_be(v.rl);
+    return v;
   }
+  Val load(const uint8_t* id, const uint8_t*) const { return load_exact(id); }
 
-  // `next` += 1 in its last `width` bytes; no successor at 99..9
-  void advance() {
-    const size_t w = runs.back().width;
-    size_t i = next.size();
-    for (size_t k = 0; k < w; ++k) {
-      char& c = next[--i];
-      if (c != '9') {
-        ++c;
-        return;
-      }
-      c = '0';
-    }
-    has_next = false;
+  bool less(const Val& a, const Val& b) const {
+    return a.kh < b.kh || (a.kh == b.kh && a.kl < b.kl);
   }
-
-  // the last run grew by k IDs, each the decimal successor of the one before
-  // it within the run's digits, the first of them being `next`; `last` is
-  // the k-th
-  void extend(size_t k, const uint8_t* last, size_t len) {
-    if (!k || !ok || !has_next) return;
-    runs.back().count += k;
-    n += k;
-    next.assign((const char*)last, len);
-    advance();
+  bool successor(const Val& a, const Val& b) const {
+    const uint64_t d = b.kl - a.kl;
+    const unsigned d0 = (unsigned)(a.kl & 0xFF) - '0';
+    return a.kh == b.kh && ((d == 1 && d0 < 9) ||
+                            (d == 247 && d0 == 9 && (unsigned)(((a.kl >> 8) & 0xFF) - '0') < 9));
   }
-
-  void add(const uint8_t* id, size_t len) {
-    if (!ok) return;
-    ++n;
-    if (has_next && len == next.size() && memcmp(id, next.data(), len) == 0) {
-      ++runs.back().count;
-      advance();
-      return;
-    }
-    size_t w = 0;
-    while (w < len && (unsigned)(id[len - 1 - w] - '0') < 10) ++w;
-    if (w == 0 || w > kRunsMaxWidth || runs.size() >= max_runs) {
-      ok = false;
-      return;
-    }
-    const size_t plen = len - w;
-    for (size_t i = 0; i < plen; ++i) {
-      const uint8_t c = id[i];
-      if (c < 0x20 || c >= 0x80 || c == '"' || c == '\\') {
-        ok = false;
-        return;
-      }
-    }
-    uint64_t v = 0;
-    for (size_t i = plen; i < len; ++i) v = v * 10 + (id[i] - '0');
-    IdRun r;
-    r.prefix_len = plen;
-    r.width = (unsigned)w;
-    r.start = v;
-    r.count = 1;
-    if (!runs.empty() && runs.back().prefix_len == plen &&
-        memcmp(prefixes.data() + runs.back().prefix_off, id, plen) == 0) {
-      r.prefix_off = runs.back().prefix_off;
-    } else {
-      r.prefix_off = prefixes.size();
-      prefixes.append((const char*)id, plen);
-    }
-    runs.push_back(r);
-    next.assign((const char*)id, len);
-    has_next = true;
-    advance();
+  bool needs_escape(const Val& v) const {
+    return word_needs_escape(v.kh) || word_needs_escape(v.kl);
   }
-
-  bool qualifies() const {
-    return ok && n >= kRunsMinIds && runs.size() * kRunsPerIds <= n;
-  }
-
-  // compact JSON: [["0-",6,0,18432]]
-  void to_json(std::string& out) const {
-    out.clear();
-    out.push_back('[');
-    char num[24];
-    for (size_t i = 0; i < runs.size(); ++i) {
-      const IdRun& r = runs[i];
-      if (i) out.push_back(',');
-      out.append("[\"");
-      out.append(prefixes, r.prefix_off, r.prefix_len);
-      out.append("\",");
-      const uint64_t f[3] = {r.width, r.start, r.count};
-      for (int k = 0; k < 3; ++k) {
-        char* e = num + sizeof num;
-        uint64_t v = f[k];
-        do {
-          *--e = (char)('0' + v % 10);
-          v /= 10;
-        } while (v);
-        out.append(e, num + sizeof num - e);
-        out.push_back(k < 2 ? ',' : ']');
-      }
-    }
-    out.push_back(']');
+  void store(char* out, const Val& v) const {
+    memcpy(out, &v.rh, 8);
+    memcpy(out + off, &v.rl, 8);
   }
 };
+
+// the JSON literal of an ID without bytes to escape; the closing quote goes
+// in after the whole-word store, which may cover its place
+template <class K>
+inline char* put_literal(const K& k, char* q, const typename K::Val& v) {
+  q[0] = '"';
+  k.store(q + 1, v);
+  q[k.L + 1] = '"';
+  return q + k.L + 2;
+}
 
 // The strings are used as raw storage: size() is the high-water mark of what
 // was ever needed (so growing zero-fills only new bytes), and each call
@@ -365,7 +301,7 @@ struct DigestScratch {
   std::string json;
   std::vector<Span> spans;
   std::vector<uint64_t> keys;  // radix fallback: n keys + n for the passes
-  RunBuilder runs;             // digest_field_runs and the two memo digests
+  RunBuilder runs;             // digest_field_split
 
   void trim() {
     if (joined.capacity() > kScratchCap) std::string().swap(joined);
@@ -516,152 +452,81 @@ struct DigestWriter {
   bool run(Reader& r, uint8_t tagbyte, size_t L, Span& prev, size_t& count,
            std::vector<Span>* spans) {
     const size_t stride = L + 2;
-    const uint8_t* p = r.p;
-    const uint8_t* const end = r.end;
-    const size_t maxn = (size_t)(end - p) / stride;
-    if (maxn == 0 || p[0] != tagbyte || p[1] != L) return true;
+    const size_t maxn = (size_t)(r.end - r.p) / stride;
+    if (maxn == 0 || r.p[0] != tagbyte || r.p[1] != L) return true;
     // room for the whole run, once: per entry a separator and L bytes
     // (joined), a comma, two quotes and L bytes (JSON), plus the word slack
     if ((size_t)(jo_end - jo) < maxn * (L + 1) + kWordSlack)
       throw std::runtime_error("digest overflow");
     if (want_json) json_room(maxn * (L + 3) + 1 + kWordSlack);
-    char* j = jo;
-    char* q = js;
-    const bool json = want_json;
-    const uint8_t* last = nullptr;
-    size_t n = 0;
-    bool in_order = true;
-    // runs: an entry that is its predecessor with the last digit one higher
-    // is only counted; every other one goes through RunBuilder::add
-    RunBuilder* rbl = rb && rb->ok ? rb : nullptr;
-    size_t matched = 0;
-    if (L <= 8) {
-      const int sh = 64 - 8 * (int)L;
-      const uint64_t unit = 1ull << sh;
-      // x9 -> y0 in the last two bytes: + 256 units - 9 units
-      const uint64_t carry = 247 * unit;
-      const int sh1 = L >= 2 ? sh + 8 : sh;  // the digit before the last
-      const uint64_t mask = ~0ull << (64 - 8 * L);
-      // the bytes past the ID must not look like bytes to escape
-      const uint64_t pad = ~mask & 0x3030303030303030ull;
-      uint64_t pk = be_key_bytes(prev.first, L);
-      while ((size_t)(end - p) >= stride && p[0] == tagbyte && p[1] == L) {
+    // One loop for both key widths. The cursors are copied into locals around
+    // the stores, and so is everything else the loop reads: a store through a
+    // char* may alias the members and the captures, which would then be
+    // reloaded after each.
+    auto walk = [&](const auto k) {
+      const size_t len = k.L, step = len + 2;
+      const uint8_t tag = tagbyte;
+      std::vector<Span>* const sp = spans;
+      const uint8_t* p = r.p;
+      const uint8_t* const end = r.end;
+      char* j = jo;
+      char* q = js;
+      const bool json = want_json;
+      const uint8_t* last = nullptr;
+      size_t n = 0;
+      bool in_order = true;
+      // runs: an entry that is its predecessor's successor is only counted;
+      // every other one goes through RunBuilder::add
+      RunBuilder* rbl = rb && rb->ok ? rb : nullptr;
+      size_t matched = 0;
+      auto pv = k.load_exact(prev.first);
+      while ((size_t)(end - p) >= step && p[0] == tag && p[1] == len) {
         const uint8_t* pay = p + 2;
-        uint64_t raw = 0;
-        if ((size_t)(end - pay) >= 8)
-          memcpy(&raw, pay, 8);
-        else
-          memcpy(&raw, pay, L);  // the last entries of a range: L bytes only
-        const uint64_t key = word_to_be(raw) & mask;
-        if (key < pk) {
+        const auto v = k.load(pay, end);
+        if (k.less(v, pv)) {
           in_order = false;
           break;
         }
         if (rbl) {
-          const uint64_t d = key - pk;
-          const unsigned d0 = (unsigned)((pk >> sh) & 0xFF) - '0';
-          if ((d == unit && d0 < 9) ||
-              (d == carry && d0 == 9 && L >= 2 &&
-               (unsigned)(((pk >> sh1) & 0xFF) - '0') < 9)) {
+          if (k.successor(pv, v)) {
             ++matched;
           } else {
-            rbl->extend(matched, last, L);
+            rbl->extend(matched, last, len);
             matched = 0;
-            rbl->add(pay, L);
+            rbl->add(pay, len);
             if (!rbl->ok) rbl = nullptr;
           }
         }
-        pk = key;
+        pv = v;
         *j = ':';
-        memcpy(j + 1, &raw, 8);
-        j += L + 1;
+        k.store(j + 1, v);
+        j += len + 1;
         if (json) {
-          if (word_needs_escape(key | pad)) {
+          if (k.needs_escape(v)) {
             js = q;
-            json_room(6 * L + 4 + ((size_t)(end - p) / stride) * (L + 3) + kWordSlack);
+            json_room(6 * len + 4 + ((size_t)(end - p) / step) * (len + 3) + kWordSlack);
             q = js;
             *q++ = ',';
-            q = json_put_string(q, pay, L);
+            q = json_put_string(q, pay, len);
           } else {
-            q[0] = ',';
-            q[1] = '"';
-            memcpy(q + 2, &raw, 8);
-            q[L + 2] = '"';
-            q += L + 3;
+            *q = ',';
+            q = put_literal(k, q + 1, v);
           }
         }
-        if (spans) spans->emplace_back(pay, L);
+        if (sp) sp->emplace_back(pay, len);
         last = pay;
         ++n;
-        p += stride;
+        p += step;
       }
-    } else {
-      // two overlapping words: the first 8 bytes, then the last 8
-      const size_t off = L - 8;
-      uint64_t raw;
-      memcpy(&raw, prev.first, 8);
-      uint64_t ph = word_to_be(raw);
-      memcpy(&raw, prev.first + off, 8);
-      uint64_t pl = word_to_be(raw);
-      while ((size_t)(end - p) >= stride && p[0] == tagbyte && p[1] == L) {
-        const uint8_t* pay = p + 2;
-        uint64_t rh, rl;
-        memcpy(&rh, pay, 8);
-        memcpy(&rl, pay + off, 8);
-        const uint64_t kh = word_to_be(rh), kl = word_to_be(rl);
-        if (kh < ph || (kh == ph && kl < pl)) {
-          in_order = false;
-          break;
-        }
-        if (rbl) {
-          const uint64_t d = kl - pl;
-          const unsigned d0 = (unsigned)(pl & 0xFF) - '0';
-          if (kh == ph && ((d == 1 && d0 < 9) ||
-                           (d == 247 && d0 == 9 &&
-                            (unsigned)(((pl >> 8) & 0xFF) - '0') < 9))) {
-            ++matched;
-          } else {
-            rbl->extend(matched, last, L);
-            matched = 0;
-            rbl->add(pay, L);
-            if (!rbl->ok) rbl = nullptr;
-          }
-        }
-        ph = kh;
-        pl = kl;
-        *j = ':';
-        memcpy(j + 1, &rh, 8);
-        memcpy(j + 1 + off, &rl, 8);
-        j += L + 1;
-        if (json) {
-          if (word_needs_escape(kh) || word_needs_escape(kl)) {
-            js = q;
-            json_room(6 * L + 4 + ((size_t)(end - p) / stride) * (L + 3) + kWordSlack);
-            q = js;
-            *q++ = ',';
-            q = json_put_string(q, pay, L);
-          } else {
-            q[0] = ',';
-            q[1] = '"';
-            memcpy(q + 2, &rh, 8);
-            memcpy(q + 2 + off, &rl, 8);
-            q[L + 2] = '"';
-            q += L + 3;
-          }
-        }
-        if (spans) spans->emplace_back(pay, L);
-        last = pay;
-        ++n;
-        p += stride;
-      }
-    }
-    if (rbl) rbl->extend(matched, last, L);
-    jo = j;
-    js = q;
-    r.p = p;
-    count += n;
-    if (last) prev = Span{last, L};
-    return in_order;
+      if (rbl) rbl->extend(matched, last, len);
+      jo = j;
+      js = q;
+      r.p = p;
+      count += n;
+      if (last) prev = Span{last, len};
+      return in_order;
+    };
+    return L <= 8 ? walk(NarrowKey(L)) : walk(WideKey(L));
   }
 
   // Radix fallback output: the n sorted left-aligned big-endian keys of IDs
@@ -672,59 +537,43 @@ struct DigestWriter {
     if (want_json) json_room(n * (L + 3) + 1 + kWordSlack);
     char* j = jo;
     char* q = js;
-    const uint64_t pad = L == 8 ? 0 : (0x3030303030303030ull >> (8 * L));
+    const NarrowKey k(L);
     RunBuilder* rbl = rb && rb->ok ? rb : nullptr;
     size_t matched = 0;
-    const int sh = 64 - 8 * (int)L;
-    const uint64_t unit = 1ull << sh;
-    const uint64_t carry = 247 * unit;  // x9 -> y0, as in run()
-    const int sh1 = L >= 2 ? sh + 8 : sh;
-    uint8_t id[8];  // the previous key's bytes, when IDs went by uncounted
+    uint8_t id[8];  // a key's bytes, for the RunBuilder and the escape detour
     for (size_t i = 0; i < n; ++i) {
-      const uint64_t key = keys[i];
-      const uint64_t raw = word_to_be(key);
+      const NarrowKey::Val v = NarrowKey::of(keys[i]);
       if (i) *j++ = ':';
-      memcpy(j, &raw, 8);
+      k.store(j, v);
       j += L;
       if (rbl) {
-        const uint64_t pk = i ? keys[i - 1] : 0;
-        const uint64_t d = key - pk;
-        const unsigned d0 = (unsigned)((pk >> sh) & 0xFF) - '0';
-        if (i && ((d == unit && d0 < 9) ||
-                  (d == carry && d0 == 9 && L >= 2 &&
-                   (unsigned)(((pk >> sh1) & 0xFF) - '0') < 9))) {
+        if (i && k.successor(NarrowKey::of(keys[i - 1]), v)) {
           ++matched;
         } else {
           if (matched) {
-            const uint64_t praw = word_to_be(pk);
-            memcpy(id, &praw, 8);
+            k.store((char*)id, NarrowKey::of(keys[i - 1]));
             rbl->extend(matched, id, L);
             matched = 0;
           }
-          memcpy(id, &raw, 8);
+          k.store((char*)id, v);
           rbl->add(id, L);
           if (!rbl->ok) rbl = nullptr;
         }
       }
       if (want_json) {
         if (i) *q++ = ',';
-        if (word_needs_escape(key | pad)) {
-          uint8_t id[8];
-          memcpy(id, &raw, 8);
+        if (k.needs_escape(v)) {
+          k.store((char*)id, v);
           js = q;
           json_room(6 * L + 4 + (n - i) * (L + 3) + kWordSlack);
           q = json_put_string(js, id, L);
         } else {
-          q[0] = '"';
-          memcpy(q + 1, &raw, 8);
-          q[L + 1] = '"';
-          q += L + 2;
+          q = put_literal(k, q, v);
         }
       }
     }
     if (rbl && matched) {
-      const uint64_t praw = word_to_be(keys[n - 1]);
-      memcpy(id, &praw, 8);
+      k.store((char*)id, NarrowKey::of(keys[n - 1]));
       rbl->extend(matched, id, L);
     }
     jo = j;
@@ -818,7 +667,7 @@ inline DigestOut digest_ranges(DigestScratch& s, const Span* ranges, size_t nran
     // bounds check of the walk), sort byte-wise shorter-prefix-first, join
     s.spans.clear();
     for (size_t ri = 0; ri < nranges; ++ri)
-      spanN(ranges[ri].first, ranges[ri].first + ranges[ri].second, want, s.spans);
+      spans_of(ranges[ri].first, ranges[ri].first + ranges[ri].second, want, s.spans);
     count = s.spans.size();
     w.restart();
     // one length 1 <= L <= 8 throughout: sort big-endian words, not spans
@@ -830,21 +679,15 @@ inline DigestOut digest_ranges(DigestScratch& s, const Span* ranges, size_t nran
       if (s.keys.size() < 2 * count) s.keys.resize(2 * count);
       uint64_t* keys = s.keys.data();
       // spans come in range order; a whole-word load must stay in its range
+      const NarrowKey k(L);
       size_t i = 0;
       for (size_t ri = 0; ri < nranges && i < count; ++ri) {
         const uint8_t* lo = ranges[ri].first;
         const uint8_t* hi = lo + ranges[ri].second;
-        const uint64_t mask = ~0ull << (64 - 8 * L);
         for (; i < count; ++i) {
           const uint8_t* id = s.spans[i].first;
           if (id < lo || id >= hi) break;
-          if ((size_t)(hi - id) >= 8) {
-            uint64_t raw;
-            memcpy(&raw, id, 8);
-            keys[i] = word_to_be(raw) & mask;
-          } else {
-            keys[i] = be_key_bytes(id, L);
-          }
+          keys[i] = k.load(id, hi).key;
         }
       }
       for (; i < count; ++i) keys[i] = be_key_bytes(s.spans[i].first, L);
@@ -866,132 +709,18 @@ inline DigestOut digest_field(DigestScratch& s, const uint8_t* p, size_t len,
   return digest_ranges(s, &range, 1, want, want_json, want_spans, sha);
 }
 
-// digest_field for a caller that stores runs: scratch.json[0, json_len) holds
-// the runs fragment and *is_runs is set when the set qualifies, the literal
-// list fragment otherwise. A set that qualifies never has its literal list
-// built. One that is large enough to try and then does not qualify (an ID
-// that is not run-encodable, too many runs) is walked a second time for the
-// list, without hashing again.
-inline DigestOut digest_field_runs(DigestScratch& s, const uint8_t* p, size_t len,
-                                   uint32_t want, Sha256Fn sha, bool* is_runs) {
-  *is_runs = false;
-  // an entry takes >= 3 wire bytes (tag, length, one digit)
-  if (len < 3 * kRunsMinIds) return digest_field(s, p, len, want, true, false, sha);
+// The walk of the two digests below: [p, p + len) with the scratch
+// RunBuilder, hashed where `sha` is given. True when the set qualifies as
+// runs; its fragment is then in scratch.json (and no literal list was built).
+inline bool digest_field_split(DigestScratch& s, const uint8_t* p, size_t len,
+                               uint32_t want, Sha256Fn sha, DigestOut& d) {
   Span range{p, len};
   s.runs.reset(len / (3 * kRunsPerIds));
-  DigestOut d = digest_ranges(s, &range, 1, want, false, false, sha, &s.runs);
-  if (s.runs.qualifies() && s.runs.n == d.count) {
-    s.runs.to_json(s.json);
-    d.json_len = s.json.size();
-    *is_runs = true;
-    return d;
-  }
-  DigestOut l = digest_ranges(s, &range, 1, want, true, false, nullptr);
-  d.json_len = l.json_len;
-  return d;
+  d = digest_ranges(s, &range, 1, want, false, false, sha, &s.runs);
+  if (!s.runs.qualifies() || s.runs.n != d.count) return false;
+  s.runs.to_json(s.json);
+  return true;
 }
-
-// ---- hash memo ----------------------------------------------------------------
-// Allocate and PreStart hash the same device set moments apart. For a set
-// that qualifies as runs, the runs fragment is an exact name of the sorted
-// list (expand_runs rebuilds it byte for byte), so equal fragments mean equal
-// joined bytes and equal hashes: Allocate leaves fragment -> hash here and
-// PreStart takes it instead of hashing again. A hit removes the entry, so
-// every skipped hash stands for one hash Allocate really computed.
-//
-// Bounds: at most `cap` entries (kMemoEntries by default, 0 = off), keys of
-// at most kMemoMaxKey bytes (a longer fragment is not stored and its PreStart
-// hashes), so the memo holds about 1 MiB of keys at the most. At the cap the
-// oldest entry goes. One mutex guards it: digests run without the GIL on
-// several server threads, and the critical sections are a lookup and a copy
-// of ~100 bytes.
-
-constexpr size_t kMemoEntries = 256;
-constexpr size_t kMemoMaxKey = 4096;
-
-struct HashMemoStats {
-  uint64_t puts = 0, hits = 0, misses = 0, evictions = 0;
-  size_t entries = 0, cap = 0;
-};
-
-class HashMemo {
- public:
-  // 0 turns the memo off and empties it; a smaller cap drops the oldest
-  void configure(size_t entries) {
-    std::lock_guard<std::mutex> g(mu_);
-    cap_ = entries;
-    while (order_.size() > cap_) drop_oldest();
-  }
-
-  // unlocked peek for the callers' fast path; put and take check again
-  bool enabled() const { return cap_.load(std::memory_order_relaxed) != 0; }
-
-  void put(std::string_view key, const char hex[8]) {
-    if (key.size() > kMemoMaxKey) return;
-    std::lock_guard<std::mutex> g(mu_);
-    if (!cap_) return;
-    ++stats_.puts;
-    auto it = index_.find(key);
-    if (it != index_.end()) {
-      // the same set again: one entry, now the newest
-      memcpy(it->second->hex, hex, 8);
-      order_.splice(order_.end(), order_, it->second);
-      return;
-    }
-    if (order_.size() >= cap_) {
-      drop_oldest();
-      ++stats_.evictions;
-    }
-    order_.emplace_back();
-    Entry& e = order_.back();
-    e.key.assign(key.data(), key.size());
-    memcpy(e.hex, hex, 8);
-    index_.emplace(std::string_view(e.key), std::prev(order_.end()));
-  }
-
-  // on a hit copies the hash (NUL-terminated) and removes the entry
-  bool take(std::string_view key, char hex[9]) {
-    std::lock_guard<std::mutex> g(mu_);
-    if (!cap_) return false;
-    auto it = key.size() <= kMemoMaxKey ? index_.find(key) : index_.end();
-    if (it == index_.end()) {
-      ++stats_.misses;
-      return false;
-    }
-    ++stats_.hits;
-    memcpy(hex, it->second->hex, 8);
-    hex[8] = 0;
-    auto node = it->second;
-    index_.erase(it);  // before the node that owns the key's bytes
-    order_.erase(node);
-    return true;
-  }
-
-  HashMemoStats stats() {
-    std::lock_guard<std::mutex> g(mu_);
-    HashMemoStats s = stats_;
-    s.entries = order_.size();
-    s.cap = cap_;
-    return s;
-  }
-
- private:
-  struct Entry {
-    std::string key;
-    char hex[8];
-  };
-
-  void drop_oldest() {
-    index_.erase(std::string_view(order_.front().key));
-    order_.pop_front();
-  }
-
-  std::mutex mu_;
-  std::atomic<size_t> cap_{kMemoEntries};
-  std::list<Entry> order_;  // oldest first; the index's keys view these nodes
-  std::unordered_map<std::string_view, std::list<Entry>::iterator> index_;
-  HashMemoStats stats_;
-};
 
 // Allocate side: digest_field(want_json = false) for a caller that feeds the
 // memo. A field large enough to hold a set that qualifies is walked with the
@@ -999,199 +728,40 @@ class HashMemo {
 // fragment -> hash is put. The result never differs from digest_field's.
 inline DigestOut digest_field_put(DigestScratch& s, const uint8_t* p, size_t len,
                                   uint32_t want, Sha256Fn sha, HashMemo* memo) {
+  // an entry takes >= 3 wire bytes (tag, length, one digit)
   if (len < 3 * kRunsMinIds || !memo || !memo->enabled())
     return digest_field(s, p, len, want, false, false, sha);
-  Span range{p, len};
-  s.runs.reset(len / (3 * kRunsPerIds));
-  DigestOut d = digest_ranges(s, &range, 1, want, false, false, sha, &s.runs);
-  if (s.runs.qualifies() && s.runs.n == d.count) {
-    s.runs.to_json(s.json);
-    memo->put(s.json, d.hex);
-  }
+  DigestOut d;
+  if (digest_field_split(s, p, len, want, sha, d)) memo->put(s.json, d.hex);
   return d;
 }
 
-// PreStart side: digest_field_runs for a caller that consults the memo. The
-// walk leaves the hash out; a set that qualifies takes its hash from the
-// memo, and on a miss the joined bytes the walk left in the scratch are
-// hashed. A set that does not qualify is hashed from those same bytes before
-// the second walk builds its list, so no set is walked more often than by
-// digest_field_runs and none is hashed twice.
-inline DigestOut digest_field_runs_take(DigestScratch& s, const uint8_t* p, size_t len,
-                                        uint32_t want, Sha256Fn sha, bool* is_runs,
-                                        HashMemo* memo) {
-  if (len < 3 * kRunsMinIds || !memo || !memo->enabled())
-    return digest_field_runs(s, p, len, want, sha, is_runs);
+// PreStart side: digest_field for a caller that stores runs. Where the set
+// qualifies, scratch.json[0, json_len) holds the runs fragment and *is_runs is
+// set; its literal list is never built. Otherwise the fragment is the literal
+// list: a field too small to qualify goes straight to digest_field, and a set
+// large enough to try that then does not qualify (an ID that is not
+// run-encodable, too many runs) is walked a second time for the list.
+// The first walk leaves the hash out. A set that qualifies takes its hash from
+// `memo` (may be null) when that is enabled and holds it; every other set is
+// hashed from the joined bytes that walk left in the scratch, once.
+inline DigestOut digest_field_runs(DigestScratch& s, const uint8_t* p, size_t len,
+                                   uint32_t want, Sha256Fn sha, bool* is_runs,
+                                   HashMemo* memo) {
   *is_runs = false;
-  Span range{p, len};
-  s.runs.reset(len / (3 * kRunsPerIds));
-  DigestOut d = digest_ranges(s, &range, 1, want, false, false, nullptr, &s.runs);
-  if (s.runs.qualifies() && s.runs.n == d.count) {
-    s.runs.to_json(s.json);
+  if (len < 3 * kRunsMinIds) return digest_field(s, p, len, want, true, false, sha);
+  DigestOut d;
+  if (digest_field_split(s, p, len, want, nullptr, d)) {
     d.json_len = s.json.size();
     *is_runs = true;
-    if (!memo->take(s.json, d.hex)) hash_hex8(sha, s.joined.data(), d.joined_len, d.hex);
+    if (!(memo && memo->enabled() && memo->take(s.json, d.hex)))
+      hash_hex8(sha, s.joined.data(), d.joined_len, d.hex);
     return d;
   }
   hash_hex8(sha, s.joined.data(), d.joined_len, d.hex);
-  DigestOut l = digest_ranges(s, &range, 1, want, true, false, nullptr);
-  d.json_len = l.json_len;
+  Span range{p, len};
+  d.json_len = digest_ranges(s, &range, 1, want, true, false, nullptr).json_len;
   return d;
-}
-
-// ---- runs -> literal list ----------------------------------------------------
-// parse_runs checks a runs fragment against the ID count its record states
-// and sizes the expansion; write_runs then fills exactly plan.total bytes.
-// Nothing is allocated for the expansion before every check has passed:
-// counts must sum to expected_count, start + count <= 10^width, width in
-// 1..18, total <= kScratchCap. Prefix spans point into the fragment.
-
-struct RunsPlan {
-  struct Run {
-    const char* prefix;
-    size_t prefix_len;
-    unsigned width;
-    uint64_t start, count;
-  };
-  std::vector<Run> runs;
-  size_t total = 2;  // "[]"
-};
-
-namespace runs_detail {
-
-inline void ws(const char*& p, const char* end) {
-  while (p < end && (*p == ' ' || *p == '\t' || *p == '\n' || *p == '\r')) ++p;
-}
-
-inline void expect(const char*& p, const char* end, char c) {
-  ws(p, end);
-  if (p >= end || *p != c) throw std::runtime_error("runs: malformed fragment");
-  ++p;
-}
-
-// a JSON non-negative integer below 10^18: digits only, no leading zero
-inline uint64_t uint_field(const char*& p, const char* end) {
-  ws(p, end);
-  const char* b = p;
-  uint64_t v = 0;
-  while (p < end && (unsigned)(*p - '0') < 10) {
-    if (p - b >= 18) throw std::runtime_error("runs: number too long");
-    v = v * 10 + (uint64_t)(*p - '0');
-    ++p;
-  }
-  if (p == b || (p - b > 1 && *b == '0'))
-    throw std::runtime_error("runs: not a non-negative integer");
-  if (p < end && (*p == '.' || *p == 'e' || *p == 'E'))
-    throw std::runtime_error("runs: not an integer");
-  return v;
-}
-
-}  // namespace runs_detail
-
-inline RunsPlan parse_runs(const char* frag, size_t len, uint64_t expected_count) {
-  using namespace runs_detail;
-  static const uint64_t kPow10[19] = {
-      1ull, 10ull, 100ull, 1000ull, 10000ull, 100000ull, 1000000ull, 10000000ull,
-      100000000ull, 1000000000ull, 10000000000ull, 100000000000ull, 1000000000000ull,
-      10000000000000ull, 100000000000000ull, 1000000000000000ull, 10000000000000000ull,
-      100000000000000000ull, 1000000000000000000ull};
-  RunsPlan plan;
-  const char* p = frag;
-  const char* const end = frag + len;
-  uint64_t left = expected_count;
-  expect(p, end, '[');
-  ws(p, end);
-  if (p < end && *p == ']') {
-    ++p;
-  } else {
-    for (;;) {
-      RunsPlan::Run r;
-      expect(p, end, '[');
-      expect(p, end, '"');
-      r.prefix = p;
-      while (p < end && *p != '"') {
-        const unsigned char c = (unsigned char)*p;
-        if (c < 0x20 || c >= 0x80 || c == '\\') throw std::runtime_error("runs: bad prefix");
-        ++p;
-      }
-      r.prefix_len = (size_t)(p - r.prefix);
-      expect(p, end, '"');
-      expect(p, end, ',');
-      const uint64_t width = uint_field(p, end);
-      expect(p, end, ',');
-      r.start = uint_field(p, end);
-      expect(p, end, ',');
-      r.count = uint_field(p, end);
-      expect(p, end, ']');
-      if (width < 1 || width > kRunsMaxWidth) throw std::runtime_error("runs: bad width");
-      r.width = (unsigned)width;
-      if (r.count < 1 || r.count > left) throw std::runtime_error("runs: count mismatch");
-      left -= r.count;
-      // r.start, r.count < 10^18 each: the sum fits a uint64
-      if (r.start + r.count > kPow10[width]) throw std::runtime_error("runs: past the width");
-      // r.count <= kScratchCap from here on, so the product cannot wrap
-      if (r.count > kScratchCap) throw std::runtime_error("runs: too large");
-      const uint64_t per = (uint64_t)r.prefix_len + width + 3;  // quotes, comma
-      if (per > kScratchCap || r.count * per > kScratchCap - plan.total)
-        throw std::runtime_error("runs: too large");
-      plan.total += (size_t)(r.count * per);
-      plan.runs.push_back(r);
-      ws(p, end);
-      if (p < end && *p == ',') {
-        ++p;
-        continue;
-      }
-      expect(p, end, ']');
-      break;
-    }
-    plan.total -= 1;  // no comma after the last ID
-  }
-  ws(p, end);
-  if (p != end) throw std::runtime_error("runs: trailing bytes");
-  if (left) throw std::runtime_error("runs: count mismatch");
-  return plan;
-}
-
-// the literal list fragment, json.dumps(ids, separators=(",", ":")), into
-// out[0, plan.total)
-inline void write_runs(const RunsPlan& plan, char* out) {
-  char* q = out;
-  *q++ = '[';
-  bool first = true;
-  for (const RunsPlan::Run& r : plan.runs) {
-    char digits[kRunsMaxWidth];
-    uint64_t v = r.start;
-    for (unsigned i = r.width; i-- > 0;) {
-      digits[i] = (char)('0' + v % 10);
-      v /= 10;
-    }
-    for (uint64_t k = 0; k < r.count; ++k) {
-      if (!first) *q++ = ',';
-      first = false;
-      *q++ = '"';
-      memcpy(q, r.prefix, r.prefix_len);
-      q += r.prefix_len;
-      memcpy(q, digits, r.width);
-      q += r.width;
-      *q++ = '"';
-      for (unsigned i = r.width; i-- > 0;) {  // digits += 1
-        if (digits[i] != '9') {
-          ++digits[i];
-          break;
-        }
-        digits[i] = '0';
-      }
-    }
-  }
-  *q++ = ']';
-  if ((size_t)(q - out) != plan.total) throw std::logic_error("runs: size mismatch");
-}
-
-inline std::string expand_runs(const char* frag, size_t len, uint64_t expected_count) {
-  RunsPlan plan = parse_runs(frag, len, expected_count);
-  std::string out(plan.total, '\0');
-  write_runs(plan, &out[0]);
-  return out;
 }
 
 }  // namespace wirecore

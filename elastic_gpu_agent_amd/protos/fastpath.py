@@ -154,9 +154,9 @@ def decode_prestart_request_digest(buf: bytes) -> dict:
 # For a set that is stored as runs, the runs fragment names the sorted list
 # exactly, so the native Allocate digest leaves fragment -> hash in a bounded
 # per-process memo and the PreStart digest takes it (and removes it) instead
-# of hashing the same ~200 KB again; a miss only hashes (native/wirecore.h,
-# "hash memo"). The pure-Python codecs have no memo.
-HASH_MEMO_ENTRIES = 256  # wirecore.h kMemoEntries
+# of hashing the same ~200 KB again; a miss only hashes (native/hashmemo.h).
+# The pure-Python codecs have no memo.
+HASH_MEMO_ENTRIES = 256  # hashmemo.h kMemoEntries
 
 
 def hash_memo_configure(entries: int) -> None:
@@ -176,7 +176,7 @@ def hash_memo_stats() -> dict:
 # ---- ID runs: how the store keeps a large device set -----------------------
 # A sorted set of mostly consecutive IDs ("0-000000" .. "0-018431") is kept as
 # [[prefix, width, start, count], ...] instead of its literal list. The rules
-# (native/wirecore.h, "ID runs"): an ID is run-encodable when it ends in a
+# (native/idruns.h): an ID is run-encodable when it ends in a
 # maximal run of 1..18 ASCII digits and holds no byte json.dumps would escape;
 # an ID with the prefix and width of its predecessor and value == previous + 1
 # extends the run, anything else starts one; a set is stored as runs only
@@ -186,7 +186,7 @@ def hash_memo_stats() -> dict:
 RUNS_MIN_IDS = 1024
 RUNS_PER_IDS = 8
 RUNS_MAX_WIDTH = 18
-RUNS_MAX_EXPANDED = 4 << 20  # wirecore.h kScratchCap
+RUNS_MAX_EXPANDED = 4 << 20  # idruns.h kRunsMaxExpanded
 
 
 def _split_run_id(s: str):

@@ -5,7 +5,7 @@ The libFuzzer harness (native/fuzz_targets.cpp, built by
 with ASan; this replay keeps every interesting/crashing input from past
 fuzzing sessions in the normal CPU suite. First catch: a 64-bit
 length-varint pointer-wrap OOB read in the wire walker
-(wirecore.h Reader/field1_spans — fixed; the crash input is in the corpus).
+(wirecore.h Reader/spans_of — fixed; the crash input is in the corpus).
 """
 import glob
 import os

@@ -1,4 +1,4 @@
-"""The Allocate -> PreStart hash memo of _fastwire (native/wirecore.h, "hash
+"""The Allocate -> PreStart hash memo of _fastwire (native/hashmemo.h, "hash
 memo"): Allocate's digest leaves runs fragment -> hash, PreStart's digest takes
 it instead of hashing again. Every result is checked against
 types.hash_device_ids and against the same call with the memo off."""

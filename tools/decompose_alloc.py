@@ -13,6 +13,8 @@ through the Python calls and through the native ones.
 
   python tools/decompose_alloc.py              # 18,432 IDs: the mixed config
   python tools/decompose_alloc.py --ids 73728  # a 72-GiB pod at 1-MiB units
+  python tools/decompose_alloc.py --id-format "0-{:011d}"  # 13-byte IDs: the
+                                               # digest's two-word keys
 
 Run from the repository root.
 """
@@ -31,13 +33,15 @@ ap.add_argument("--ids", type=int, default=18432,
 ap.add_argument("--calls", type=int, default=300, help="timed calls per row")
 ap.add_argument("--no-preferred", action="store_true",
                 help="skip the 295k-pool GetPreferredAllocation row")
+ap.add_argument("--id-format", default="0-{:06d}",
+                help="str.format pattern of a device ID (default: 0-{:06d})")
 args = ap.parse_args()
 
 tmp = tempfile.mkdtemp(); h = Harness(tmp, gpus=1, mem_unit_mib=1)
 h.plugin.memory_server.serve(); h.plugin.memory_server.wait_ready()
 ch = egrpc.Channel(h.plugin.memory_server.socket_path)
 raw = ch.unary_unary(dp.METHOD_ALLOCATE)
-ids = [f"0-{i:06d}" for i in range(args.ids)]
+ids = [args.id_format.format(i) for i in range(args.ids)]
 enc = fastpath.encode_allocate_request({"container_requests":[{"devicesIDs": ids}]})
 shuffled = list(ids); random.Random(0).shuffle(shuffled)
 enc_shuf = fastpath.encode_allocate_request({"container_requests":[{"devicesIDs": shuffled}]})

@@ -48,6 +48,9 @@ def main(argv=None) -> int:
     parser.add_argument("--gpu-selftest-timeout", type=float, default=10.0,
                         help="time limit of one self-test probe; a probe that "
                              "exceeds it makes its GPU Unhealthy")
+    parser.add_argument("--gpu-selftest-matrix", action="store_true",
+                        help="each self-test probe also runs the matrix sweep: "
+                             "the FP8, FP6, FP4, INT8, F16 and 16x16 MFMA paths")
     parser.add_argument("--recordFormat", choices=["runs", "list"], default="runs",
                         help="how the state DB holds a large consecutive device "
                              "set: as ID runs, or as the literal list that "
@@ -110,6 +113,7 @@ def main(argv=None) -> int:
         workers=args.workers,
         selftest_seconds=args.gpu_selftest_seconds,
         selftest_timeout=args.gpu_selftest_timeout,
+        selftest_matrix=args.gpu_selftest_matrix,
         record_format=args.recordFormat,
         hash_memo_entries=args.hashMemoEntries,
     )

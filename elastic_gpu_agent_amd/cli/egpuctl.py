@@ -11,7 +11,7 @@ Subcommands:
                           Unhealthy); --wait blocks until empty; --repartition
                           then flips the partition and undrains
   undrain IDX             return a drained GPU to service
-  health [IDX [--run [--full] | --clear]]
+  health [IDX [--run [--full] [--matrix] | --clear]]
                           list GPU self-test records; --run probes the GPU now
                           (same runner and policy as the agent); --clear puts
                           an unhealthy GPU back in service
@@ -177,7 +177,8 @@ def cmd_health(args) -> int:
             # same runner and same policy as the agent's monitor; an operator's
             # explicit run also probes a GPU that is already unhealthy, but a
             # pass does not heal it (only --clear does)
-            result = health.subprocess_runner(args.index, args.timeout, full=args.full)
+            kw = {"matrix": True} if args.matrix else {}
+            result = health.subprocess_runner(args.index, args.timeout, full=args.full, **kw)
             rec = health.apply_result(st, args.index, result)
             print(json.dumps({k: v for k, v in rec.items() if k != "became_unhealthy"},
                              indent=2))
@@ -258,6 +259,9 @@ def main(argv=None) -> int:
                          "non-zero when the probe fails")
     he.add_argument("--full", action="store_true",
                     help="with --run: whole-LDS, 1 GiB probe for a drained or idle GPU")
+    he.add_argument("--matrix", action="store_true",
+                    help="with --run: also run the matrix sweep (fp8, fp6, fp4, int8, "
+                         "f16 and 16x16 MFMA paths)")
     he.add_argument("--clear", action="store_true",
                     help="forget the record: the GPU is advertised Healthy and probed again")
     he.add_argument("--timeout", type=float, default=60.0,

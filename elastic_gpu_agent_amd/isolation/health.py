@@ -21,7 +21,10 @@ Policy:
   --clear``). No work is launched on a card that just hung or faulted, and a
   marginal card does not flap;
 - ``hbm_status = skipped`` (the scratch allocation failed because tenants own
-  the memory) is not a failure.
+  the memory) is not a failure;
+- with ``matrix`` on (off by default) the child also runs the matrix sweep
+  (``probes.mx_selftest``: FP8, FP6, FP4, INT8, F16 and 16x16 MFMA paths) and
+  its miscompares count like any other.
 
 The agent process itself never initialises HIP: every probe is a fresh child
 started with ``subprocess``, without ``HSA_TOOLS_LIB`` in its environment, and
@@ -66,16 +69,22 @@ PERIODIC_PROBE = {"blocks": 1024, "rounds": 64, "lds_bytes": 32768, "hbm_bytes":
 # Full probe, for drained or idle GPUs: one workgroup owns the CU's whole LDS
 # and the scratch buffer is four times the Infinity Cache.
 FULL_PROBE = {"blocks": 1024, "rounds": 256, "lds_bytes": 163840, "hbm_bytes": 1 << 30}
+# Matrix sweep (probes.mx_selftest), run after the probe above when the child
+# gets --matrix. Its host reference costs 16 patterns x rounds x 3.2e5
+# multiply-adds, so rounds is small (profiles/selftest.md).
+PERIODIC_MATRIX = {"blocks": 1024, "rounds": 8}
+FULL_MATRIX = {"blocks": 1024, "rounds": 64}
 
 # test-only: EGPU_SELFTEST_INJECT=<kind>[:arg] in the CHILD's environment
 # simulates a miscompare (kind int|fma|mfma|lds with a workgroup index, or hbm
-# with a byte offset)
+# with a byte offset; or one of probes.MX_KINDS with a workgroup index, which
+# corrupts that kind of the matrix sweep)
 INJECT_ENV = "EGPU_SELFTEST_INJECT"
 
 _REPORT_KEYS = (
     "waves_run", "cus_seen", "bad_waves", "bad_kind_names", "n_bad_cus", "bad_cus",
     "lds_bytes", "hbm_status", "hbm_bytes_checked", "hbm_miscompares",
-    "hbm_first_bad_offset", "kernel_ms", "hbm_ms",
+    "hbm_first_bad_offset", "kernel_ms", "hbm_ms", "matrix",
 )
 
 
@@ -130,6 +139,15 @@ def report_failures(report: dict) -> List[str]:
     if report.get("hbm_miscompares", 0) or report.get("hbm_status") == "failed":
         why.append(f"{report.get('hbm_miscompares')} memory miscompare(s), first at byte "
                    f"{report.get('hbm_first_bad_offset')}")
+    matrix = report.get("matrix")
+    if isinstance(matrix, dict):
+        if matrix.get("bad_waves", 0):
+            kinds = ",".join(matrix.get("bad_kind_names") or []) or "?"
+            why.append(f"matrix: {matrix['bad_waves']} bad wave(s) [{kinds}] on "
+                       f"{matrix.get('n_bad_cus', '?')} CU(s)")
+        blocks = matrix.get("blocks")
+        if blocks is not None and matrix.get("waves_run") != 4 * blocks:
+            why.append(f"matrix: {matrix.get('waves_run')} of {4 * blocks} waves reported")
     return why
 
 
@@ -174,16 +192,18 @@ def apply_result(storage, gpu_index: int, result: dict, fail_threshold: int = 2,
 
 # ---------------------------------------------------------------- runner
 
-def _probe_argv(index: int, full: bool) -> List[str]:
+def _probe_argv(index: int, full: bool, matrix: bool = False) -> List[str]:
     argv = [sys.executable, "-m", "elastic_gpu_agent_amd.isolation.health",
             "--probe", str(index)]
     if full:
         argv.append("--full")
+    if matrix:
+        argv.append("--matrix")
     return argv
 
 
 def subprocess_runner(index: int, timeout: float, full: bool = False,
-                      _argv: Optional[List[str]] = None) -> dict:
+                      _argv: Optional[List[str]] = None, matrix: bool = False) -> dict:
     """Runs the probe of GPU ``index`` in a fresh child and maps what happened
     to a result: {"outcome", "reason", "report", "wall_s"}. The last line of
     the child's stdout must be one JSON object."""
@@ -192,7 +212,7 @@ def subprocess_runner(index: int, timeout: float, full: bool = False,
     root = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     env["PYTHONPATH"] = os.pathsep.join(p for p in (root, env.get("PYTHONPATH")) if p)
     t0 = time.monotonic()
-    proc = subprocess.Popen(_argv or _probe_argv(index, full), env=env,
+    proc = subprocess.Popen(_argv or _probe_argv(index, full, matrix), env=env,
                             stdin=subprocess.DEVNULL, stdout=subprocess.PIPE,
                             stderr=subprocess.PIPE, text=True)
 
@@ -233,7 +253,8 @@ class HealthMonitor:
     def __init__(self, storage, operator, runner: Callable = subprocess_runner,
                  interval: float = 600.0, fail_threshold: int = 2,
                  on_change: Optional[Callable[[], None]] = None, event_sink=None,
-                 limits=None, timeout: float = DEFAULT_TIMEOUT_SECONDS):
+                 limits=None, timeout: float = DEFAULT_TIMEOUT_SECONDS,
+                 matrix: bool = False):
         self.storage = storage
         self.operator = operator
         self.runner = runner
@@ -243,6 +264,7 @@ class HealthMonitor:
         self.event_sink = event_sink
         self.limits = limits
         self.timeout = timeout
+        self.matrix = matrix
         self._stop = threading.Event()
         self._probe_lock = threading.Lock()  # never two probes at once
         self._thread: Optional[threading.Thread] = None
@@ -262,7 +284,10 @@ class HealthMonitor:
                     continue
                 t0 = time.perf_counter()
                 try:
-                    result = self.runner(idx, self.timeout)
+                    # the keyword only when set: a runner written before the
+                    # matrix sweep takes two arguments
+                    result = (self.runner(idx, self.timeout, matrix=True) if self.matrix
+                              else self.runner(idx, self.timeout))
                 except Exception as e:  # a runner that cannot start a child
                     result = {"outcome": OUTCOME_CRASH, "reason": f"runner: {e}"}
                 GLOBAL_METRICS.recorder(GPU_SELFTEST).observe(time.perf_counter() - t0)
@@ -337,15 +362,24 @@ def _probe_main(argv: List[str]) -> int:
     p = argparse.ArgumentParser(prog="egpu-selftest-probe")
     p.add_argument("--probe", type=int, required=True, metavar="GPU")
     p.add_argument("--full", action="store_true")
+    p.add_argument("--matrix", action="store_true")
     args = p.parse_args(argv)
     from . import probes
 
     sizes = dict(FULL_PROBE if args.full else PERIODIC_PROBE)
     inject = os.environ.get(INJECT_ENV)
+    inject = _parse_inject(inject) if inject else None
+    # a matrix kind's name selects the sweep, any other name the probe above
+    # (without --matrix there is no sweep to corrupt and it does nothing)
+    mx_inject = inject if inject and inject[0] in probes.MX_KINDS else None
     seed = int(time.time()) & 0xFFFFFFFF
     report = probes.selftest(args.probe, seed=seed,
-                             _inject=_parse_inject(inject) if inject else None, **sizes)
+                             _inject=None if mx_inject else inject, **sizes)
     report.update(gpu=args.probe, blocks=sizes["blocks"], rounds=sizes["rounds"], seed=seed)
+    if args.matrix:
+        mx_sizes = dict(FULL_MATRIX if args.full else PERIODIC_MATRIX)
+        report["matrix"] = dict(
+            probes.mx_selftest(args.probe, seed=seed, _inject=mx_inject, **mx_sizes), **mx_sizes)
     print(json.dumps(report), flush=True)
     return 0
 

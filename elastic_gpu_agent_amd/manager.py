@@ -43,6 +43,8 @@ class ManagerOptions:
     # the GPUs, 0 = off; and the time limit of one probe child
     selftest_seconds: float = 0.0
     selftest_timeout: float = 10.0
+    # each probe also runs the matrix sweep (probes.mx_selftest)
+    selftest_matrix: bool = False
     # how the store's rows hold a large consecutive device set: "runs"
     # (ID runs) or "list" (the reference-format record; the way back for a
     # rollback to a build that cannot read runs)
@@ -208,6 +210,7 @@ class GPUManager:
             event_sink=self.config.event_sink,
             limits=self.config.limits,
             timeout=self.opts.selftest_timeout,
+            matrix=self.opts.selftest_matrix,
         )
         self.health_monitor.start()
 

@@ -101,10 +101,11 @@ def build_shim(force=False):
 
 
 def build_kernels(force=False):
-    srcs = [os.path.join(HERE, "egpu_kernels.hip"), os.path.join(HERE, "egpu_selftest.hip")]
-    hdr = os.path.join(HERE, "selftest_ref.h")
+    srcs = [os.path.join(HERE, f)
+            for f in ("egpu_kernels.hip", "egpu_selftest.hip", "egpu_selftest_mx.hip")]
+    hdrs = [os.path.join(HERE, h) for h in ("selftest_ref.h", "selftest_mx_ref.h")]
     out = os.path.join(PKG, "libegpu_kernels.so")
-    if not force and _newer(out, *srcs, hdr):
+    if not force and _newer(out, *srcs, *hdrs):
         return out
     hipcc = os.path.join(ROCM, "bin", "hipcc")
     _run(

@@ -109,6 +109,14 @@ def build_ref_selftest(out=None):
     return build_selftest(out, "selftest_ref_selftest.cpp")
 
 
+def build_mx_ref_selftest(out=None):
+    """selftest_mx_ref_selftest.cpp: the host reference of the matrix sweep
+    (selftest_mx_ref.h: decoders, generator, expected signatures; no GPU
+    code), built the same way."""
+    out = out or os.path.join(REPO, "bin", "egpu-selftest-mx-ref-selftest")
+    return build_selftest(out, "selftest_mx_ref_selftest.cpp")
+
+
 def build_h2frame_selftest(out=None):
     """h2frame_selftest.cpp: the transport's receive buffer, frame parser and
     header-block builders (h2frame.h, no Python) over a socketpair, built the
@@ -138,6 +146,7 @@ if __name__ == "__main__":
         rc = rc or subprocess.call([build_stride_selftest()])
         rc = rc or subprocess.call([build_runs_selftest()])
         rc = rc or subprocess.call([build_ref_selftest()])
+        rc = rc or subprocess.call([build_mx_ref_selftest()])
         rc = rc or subprocess.call([build_h2frame_selftest()])
         rc = rc or subprocess.call([build_hash_memo_selftest()])
         sys.exit(rc or subprocess.call([build_bindfx_selftest()]))

@@ -76,6 +76,20 @@ def _lib():
         lib.egpu_mxtest_lane_regs.argtypes = [
             ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_int,
         ] + [ctypes.POINTER(ctypes.c_uint32)] * 4
+        lib.egpu_selftest_hbm.argtypes = [
+            ctypes.c_int, ctypes.c_uint64, ctypes.c_uint32,
+            ctypes.POINTER(ctypes.c_uint64), ctypes.c_int, ctypes.c_int,
+            ctypes.POINTER(_SelftestReport),
+        ]
+        lib.egpu_selftest_hbm_image.argtypes = [
+            ctypes.c_int, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p,
+        ]
+        lib.egpu_selftest_hbm_words.argtypes = [
+            ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)
+        ]
+        lib.egpu_selftest_lds_words.argtypes = [
+            ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)
+        ]
         _LIB = lib
     return _LIB
 
@@ -154,7 +168,7 @@ class _SelftestParams(ctypes.Structure):
         ("blocks", ctypes.c_int32), ("rounds", ctypes.c_int32),
         ("seed", ctypes.c_uint32), ("lds_bytes", ctypes.c_uint32),
         ("hbm_bytes", ctypes.c_uint64),
-        ("inject_kind", ctypes.c_int32), ("reserved", ctypes.c_int32),
+        ("inject_kind", ctypes.c_int32), ("inject_sub", ctypes.c_int32),
         ("inject_arg", ctypes.c_uint64),
     ]
 
@@ -173,14 +187,20 @@ class _SelftestReport(ctypes.Structure):
 
 
 def _selftest_params(blocks, rounds, lds_bytes, hbm_bytes, seed, inject) -> _SelftestParams:
-    kind, arg = 0, 0
+    kind, arg, sub = 0, 0, 0
     if inject is not None:
-        name, arg = inject
+        name, arg, *place = inject
         if name not in _INJECT_KINDS:
             raise ValueError(f"unknown injection kind {name!r}")
         kind = _INJECT_KINDS[name]
+        if place:
+            # inject_sub of egpu_selftest_params: word in bits 0..23, pass above
+            word, march_pass = place
+            if name != "lds" or not (0 <= word < 1 << 24 and 0 <= march_pass < 128):
+                raise ValueError(f"no inject_sub encoding for {inject!r}")
+            sub = word | march_pass << 24
     return _SelftestParams(blocks, rounds, seed & 0xFFFFFFFF, lds_bytes, hbm_bytes,
-                           kind, 0, arg)
+                           kind, sub, arg)
 
 
 def selftest(device: int = 0, blocks: int = 1024, rounds: int = 64,
@@ -191,7 +211,9 @@ def selftest(device: int = 0, blocks: int = 1024, rounds: int = 64,
     verify pattern over `hbm_bytes` of scratch (0 = off). Bad arguments raise
     ProbeError before any HIP call. `_inject` = (kind, arg) simulates a
     miscompare (tests only): kind int/fma/mfma/lds with a workgroup index, or
-    hbm with a byte offset."""
+    hbm with a byte offset. ("lds", wg, word, pass) flips that word of the
+    march in that pass (0 = pattern, 1 = complement) instead of word 0 of
+    pass 0."""
     params = _selftest_params(blocks, rounds, lds_bytes, hbm_bytes, seed, _inject)
     rep = _SelftestReport()
     _check(_lib().egpu_selftest(device, ctypes.byref(params), ctypes.byref(rep)),
@@ -216,10 +238,11 @@ def selftest(device: int = 0, blocks: int = 1024, rounds: int = 64,
 
 
 def selftest_records(device: int = 0, blocks: int = 16, rounds: int = 64,
-                     lds_bytes: int = 32768, seed: int = 0) -> List[tuple]:
+                     lds_bytes: int = 32768, seed: int = 0, _inject=None) -> List[tuple]:
     """The raw per-wave records of one compute run, in wave order:
-    (cu_id, int_sig, fma_sig, mfma_sig, lds_bad)."""
-    params = _selftest_params(blocks, rounds, lds_bytes, 0, seed, None)
+    (cu_id, int_sig, fma_sig, mfma_sig, lds_bad). `_inject` as for selftest
+    (tests only; not hbm, no memory check runs here)."""
+    params = _selftest_params(blocks, rounds, lds_bytes, 0, seed, _inject)
     n = blocks * 4 if blocks > 0 else 0
     buf = (ctypes.c_uint32 * max(1, n * 5))()
     _check(_lib().egpu_selftest_records(device, ctypes.byref(params), buf, n),
@@ -234,6 +257,61 @@ def selftest_expected(seed: int = 0, rounds: int = 64) -> List[tuple]:
     _check(_lib().egpu_selftest_expected(seed & 0xFFFFFFFF, rounds, out),
            "egpu_selftest_expected")
     return [tuple(out[3 * p: 3 * p + 3]) for p in range(64)]
+
+
+def _hbm_fields(rep: _SelftestReport) -> dict:
+    return {
+        "hbm_status": _HBM_STATUS.get(rep.hbm_status, str(rep.hbm_status)),
+        "hbm_bytes_checked": rep.hbm_bytes_checked,
+        "hbm_miscompares": rep.hbm_miscompares,
+        "hbm_first_bad_offset": rep.hbm_first_bad_offset,
+        "hbm_ms": rep.hbm_ms,
+    }
+
+
+def selftest_hbm(device: int = 0, hbm_bytes: int = 32 << 20, seed: int = 0,
+                 corrupt=(), corrupt_pass: int = 0) -> dict:
+    """Tests only: the memory check of selftest() alone, same grid, with bit 0
+    of the words at the byte offsets `corrupt` (at most 64, distinct multiples
+    of 4 inside the buffer) flipped between the write and the verify of
+    `corrupt_pass` (0 = pattern, 1 = complement). Returns the hbm_* fields."""
+    offsets = (ctypes.c_uint64 * max(1, len(corrupt)))(*corrupt)
+    rep = _SelftestReport()
+    _check(_lib().egpu_selftest_hbm(device, hbm_bytes, seed & 0xFFFFFFFF, offsets,
+                                    len(corrupt), corrupt_pass, ctypes.byref(rep)),
+           "egpu_selftest_hbm")
+    return _hbm_fields(rep)
+
+
+SELFTEST_MAX_IMAGE = (16 << 20) + 16
+
+
+def selftest_hbm_image(device: int = 0, hbm_bytes: int = (1 << 20) + 16, seed: int = 0,
+                       march_pass: int = 0) -> bytes:
+    """Tests only: the bytes that the memory check's write launch of
+    `march_pass` leaves in a buffer of `hbm_bytes` (at most 16 MiB + 16 B)."""
+    ok = 0 < hbm_bytes <= SELFTEST_MAX_IMAGE and hbm_bytes % 16 == 0
+    out = ctypes.create_string_buffer(hbm_bytes if ok else 1)  # bad sizes: the library says so
+    _check(_lib().egpu_selftest_hbm_image(device, hbm_bytes, seed & 0xFFFFFFFF, march_pass, out),
+           "egpu_selftest_hbm_image")
+    return out.raw
+
+
+def selftest_hbm_words(first: int, n: int, seed: int = 0) -> List[int]:
+    """Host only: the four words of each of the 16-byte elements
+    first .. first+n of the memory check's pattern, in memory order."""
+    out = (ctypes.c_uint32 * max(1, 4 * n))()
+    _check(_lib().egpu_selftest_hbm_words(first, n, seed & 0xFFFFFFFF, out),
+           "egpu_selftest_hbm_words")
+    return list(out[: 4 * n])
+
+
+def selftest_lds_words(first: int, n: int, seed: int = 0) -> List[int]:
+    """Host only: words first .. first+n of the LDS march's pattern."""
+    out = (ctypes.c_uint32 * max(1, n))()
+    _check(_lib().egpu_selftest_lds_words(first, n, seed & 0xFFFFFFFF, out),
+           "egpu_selftest_lds_words")
+    return list(out[:n])
 
 
 def selftest_mfma_tile(device: int = 0, pattern: int = 0, seed: int = 0, rounds: int = 1):

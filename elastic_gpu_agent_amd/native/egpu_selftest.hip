@@ -18,7 +18,9 @@
 //                       map shows as a wrong tile, not as an opaque signature.
 //
 // inject_kind simulates a miscompare so detection is testable on a healthy
-// GPU. It corrupts data only, never an address.
+// GPU. It corrupts data only, never an address: every position it takes (a
+// workgroup, an LDS word, a byte offset) is validated against the sizes of the
+// same call before the first HIP call.
 
 #include <hip/hip_runtime.h>
 
@@ -57,6 +59,8 @@ enum { HBM_OK = 0, HBM_FAILED = 1, HBM_SKIPPED = 2, HBM_OFF = 3 };
 #define EGPU_SELFTEST_MIN_LDS 1024
 #define EGPU_SELFTEST_MAX_BLOCKS 65536
 #define EGPU_SELFTEST_MAX_HBM (64ull << 30)
+#define EGPU_SELFTEST_MAX_CORRUPT 64
+#define EGPU_SELFTEST_MAX_IMAGE ((16ull << 20) + 16)
 #define RECORD_WORDS 5
 
 extern "C" {
@@ -67,7 +71,11 @@ struct egpu_selftest_params {
   uint32_t lds_bytes;
   uint64_t hbm_bytes;  // 0 = no memory-path check
   int32_t inject_kind;
-  int32_t reserved;
+  // INJECT_LDS only (test-only, ignored by every other kind): which word of
+  // the march is flipped and in which pass. Bits 0..23 are the word index,
+  // bits 24..30 the pass (0 = pattern, 1 = complement); 0 is word 0 of the
+  // pattern pass. The word must be below lds_bytes / 4.
+  int32_t inject_sub;
   uint64_t inject_arg;  // workgroup index (int/fma/mfma/lds) or byte offset (hbm)
 };
 
@@ -127,7 +135,7 @@ __device__ inline f32x16 mfma_chain(uint32_t s, int rounds, uint32_t* last_a, ui
 
 __global__ void __launch_bounds__(256)
 selftest_kernel(uint32_t* __restrict__ out, int rounds, uint32_t seed, uint32_t lds_words,
-                int inject_kind, int inject_block) {
+                int inject_kind, int inject_block, uint32_t inject_word, int inject_pass) {
   extern __shared__ uint32_t lds[];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int pattern = (blockIdx.x * 4 + wave) & 63;
@@ -157,7 +165,8 @@ selftest_kernel(uint32_t* __restrict__ out, int rounds, uint32_t seed, uint32_t 
     const uint32_t inv = pass ? 0xffffffffu : 0u;
     for (uint32_t i = tid; i < lds_words; i += 256) lds[i] = egpu_st::lds_word(i, seed) ^ inv;
     __syncthreads();
-    if (pass == 0 && inject_kind == INJECT_LDS && inject_here && tid == 0) lds[0] ^= 1u;
+    if (pass == inject_pass && inject_kind == INJECT_LDS && inject_here && tid == 0)
+      lds[inject_word] ^= 1u;
     __syncthreads();
     for (uint32_t i = other; i < lds_words; i += 256)
       bad += lds[i] != (egpu_st::lds_word(i, seed) ^ inv);
@@ -242,6 +251,23 @@ struct Resources {
   }
 };
 
+// the compute run and the memory check time themselves with the same pair
+int create_events(Resources& res) {
+  for (hipEvent_t& e : res.ev)
+    if (e == nullptr) EGPU_CHECK(hipEventCreate(&e));
+  return 0;
+}
+
+uint32_t inject_sub_word(int32_t sub) { return (uint32_t)sub & 0xFFFFFFu; }
+int inject_sub_pass(int32_t sub) { return (int)(((uint32_t)sub >> 24) & 0x7Fu); }
+
+int validate_hbm_bytes(const char* who, uint64_t hbm_bytes, uint64_t max) {
+  if (hbm_bytes % 16 != 0 || hbm_bytes > max)
+    EGPU_BAD_ARG("%s: hbm_bytes %llu must be a multiple of 16, at most %llu", who,
+                 (unsigned long long)hbm_bytes, (unsigned long long)max);
+  return 0;
+}
+
 int validate(const egpu_selftest_params* p) {
   if (p == nullptr) EGPU_BAD_ARG("selftest: params is null");
   if (p->blocks <= 0 || p->blocks > EGPU_SELFTEST_MAX_BLOCKS)
@@ -252,9 +278,7 @@ int validate(const egpu_selftest_params* p) {
       p->lds_bytes % 4 != 0)
     EGPU_BAD_ARG("selftest: lds_bytes %u must be a multiple of 4 in [%d, %d]", p->lds_bytes,
                  EGPU_SELFTEST_MIN_LDS, EGPU_SELFTEST_MAX_LDS);
-  if (p->hbm_bytes % 16 != 0 || p->hbm_bytes > EGPU_SELFTEST_MAX_HBM)
-    EGPU_BAD_ARG("selftest: hbm_bytes %llu must be a multiple of 16, at most %llu",
-                 (unsigned long long)p->hbm_bytes, EGPU_SELFTEST_MAX_HBM);
+  if (int rc = validate_hbm_bytes("selftest", p->hbm_bytes, EGPU_SELFTEST_MAX_HBM)) return rc;
   switch (p->inject_kind) {
     case INJECT_NONE:
       break;
@@ -265,6 +289,14 @@ int validate(const egpu_selftest_params* p) {
       if (p->inject_arg >= (uint64_t)p->blocks)
         EGPU_BAD_ARG("selftest: inject_arg %llu is not a workgroup of a %d-block grid",
                      (unsigned long long)p->inject_arg, p->blocks);
+      if (p->inject_kind == INJECT_LDS) {
+        if (p->inject_sub < 0 || inject_sub_pass(p->inject_sub) > 1)
+          EGPU_BAD_ARG("selftest: inject_sub 0x%x names no pass of the LDS march (0 or 1)",
+                       (unsigned)p->inject_sub);
+        if (inject_sub_word(p->inject_sub) >= p->lds_bytes / 4)
+          EGPU_BAD_ARG("selftest: inject_sub word %u is outside the %u words of lds_bytes",
+                       inject_sub_word(p->inject_sub), p->lds_bytes / 4);
+      }
       break;
     case INJECT_HBM:
       if (p->inject_arg % 4 != 0 || p->inject_arg >= p->hbm_bytes)
@@ -288,13 +320,16 @@ int run_compute(const egpu_selftest_params* p, Resources& res, std::vector<uint3
                                    hipFuncAttributeMaxDynamicSharedMemorySize,
                                    (int)p->lds_bytes));
   const bool wg_inject = p->inject_kind >= INJECT_INT && p->inject_kind <= INJECT_LDS;
-  EGPU_CHECK(hipEventCreate(&res.ev[0]));
-  EGPU_CHECK(hipEventCreate(&res.ev[1]));
+  // validate() has checked the word against lds_bytes
+  const bool lds_inject = p->inject_kind == INJECT_LDS;
+  if (int rc = create_events(res)) return rc;
   EGPU_CHECK(hipEventRecord(res.ev[0], 0));
   hipLaunchKernelGGL(selftest_kernel, dim3(p->blocks), dim3(256), p->lds_bytes, 0,
                      (uint32_t*)res.dev[0], p->rounds, p->seed, p->lds_bytes / 4,
                      wg_inject ? p->inject_kind : INJECT_NONE,
-                     wg_inject ? (int)p->inject_arg : -1);
+                     wg_inject ? (int)p->inject_arg : -1,
+                     lds_inject ? inject_sub_word(p->inject_sub) : 0u,
+                     lds_inject ? inject_sub_pass(p->inject_sub) : 0);
   EGPU_CHECK(hipGetLastError());
   EGPU_CHECK(hipEventRecord(res.ev[1], 0));
   EGPU_CHECK(hipEventSynchronize(res.ev[1]));
@@ -310,12 +345,29 @@ void add_unique(uint32_t* ids, uint32_t* n, uint32_t cap, uint32_t id) {
   if (*n < cap) ids[(*n)++] = id;
 }
 
-int run_hbm(const egpu_selftest_params* p, Resources& res, egpu_selftest_report* rep) {
-  if (p->hbm_bytes == 0) {
+// about four elements per thread, so the grid-stride loop and its tail run
+// even on a small buffer; 4096 workgroups fill all 8 XCDs on a large one
+unsigned hbm_grid(uint64_t n16) {
+  const uint64_t grid = n16 / (256 * 4);
+  return (unsigned)(grid < 1 ? 1 : (grid > 4096 ? 4096 : grid));
+}
+
+// Words to corrupt (bit 0 flipped) between the write and the verify of one
+// pass. The caller has validated every offset: a multiple of 4 inside the
+// buffer.
+struct HbmCorruption {
+  const uint64_t* offsets;
+  int n;
+  int pass;  // 0 = pattern, 1 = complement
+};
+
+int run_hbm(uint64_t hbm_bytes, uint32_t seed, const HbmCorruption& corrupt, Resources& res,
+            egpu_selftest_report* rep) {
+  if (hbm_bytes == 0) {
     rep->hbm_status = HBM_OFF;
     return 0;
   }
-  if (hipMalloc(&res.dev[1], p->hbm_bytes) != hipSuccess) {
+  if (hipMalloc(&res.dev[1], hbm_bytes) != hipSuccess) {
     // tenants may legitimately own the memory: not a failure of the GPU
     (void)hipGetLastError();
     res.dev[1] = nullptr;
@@ -327,24 +379,22 @@ int run_hbm(const egpu_selftest_params* p, Resources& res, egpu_selftest_report*
   EGPU_CHECK(hipMemcpy(res.dev[2], init, sizeof(init), hipMemcpyHostToDevice));
   uint4* buf = (uint4*)res.dev[1];
   unsigned long long* counters = (unsigned long long*)res.dev[2];
-  const uint64_t n16 = p->hbm_bytes / 16;
-  // about four elements per thread, so the grid-stride loop and its tail run
-  // even on a small buffer; 4096 workgroups fill all 8 XCDs on a large one
-  uint64_t grid = n16 / (256 * 4);
-  grid = grid < 1 ? 1 : (grid > 4096 ? 4096 : grid);
+  const uint64_t n16 = hbm_bytes / 16;
+  const unsigned grid = hbm_grid(n16);
+  if (int rc = create_events(res)) return rc;
   EGPU_CHECK(hipEventRecord(res.ev[0], 0));
   for (int pass = 0; pass < 2; ++pass) {
     const uint32_t inv = pass ? 0xffffffffu : 0u;
-    hipLaunchKernelGGL(hbm_pattern_kernel, dim3((unsigned)grid), dim3(256), 0, 0, buf, n16,
-                       p->seed, inv, 0, counters, counters + 1);
+    hipLaunchKernelGGL(hbm_pattern_kernel, dim3(grid), dim3(256), 0, 0, buf, n16, seed, inv, 0,
+                       counters, counters + 1);
     EGPU_CHECK(hipGetLastError());
-    if (pass == 0 && p->inject_kind == INJECT_HBM) {
-      const uint64_t off = p->inject_arg;
-      const uint32_t wrong = egpu_st::hbm_word(off / 16, (int)(off % 16) / 4, p->seed) ^ 1u;
+    for (int c = 0; pass == corrupt.pass && c < corrupt.n; ++c) {
+      const uint64_t off = corrupt.offsets[c];
+      const uint32_t wrong = egpu_st::hbm_word(off / 16, (int)(off % 16) / 4, seed) ^ inv ^ 1u;
       EGPU_CHECK(hipMemcpy((char*)res.dev[1] + off, &wrong, 4, hipMemcpyHostToDevice));
     }
-    hipLaunchKernelGGL(hbm_pattern_kernel, dim3((unsigned)grid), dim3(256), 0, 0, buf, n16,
-                       p->seed, inv, 1, counters, counters + 1);
+    hipLaunchKernelGGL(hbm_pattern_kernel, dim3(grid), dim3(256), 0, 0, buf, n16, seed, inv, 1,
+                       counters, counters + 1);
     EGPU_CHECK(hipGetLastError());
   }
   EGPU_CHECK(hipEventRecord(res.ev[1], 0));
@@ -352,7 +402,7 @@ int run_hbm(const egpu_selftest_params* p, Resources& res, egpu_selftest_report*
   EGPU_CHECK(hipEventElapsedTime(&rep->hbm_ms, res.ev[0], res.ev[1]));
   unsigned long long got[2] = {0, 0};
   EGPU_CHECK(hipMemcpy(got, res.dev[2], sizeof(got), hipMemcpyDeviceToHost));
-  rep->hbm_bytes_checked = p->hbm_bytes;
+  rep->hbm_bytes_checked = hbm_bytes;
   rep->hbm_miscompares = got[0];
   rep->hbm_first_bad_offset = got[0] ? got[1] : 0;
   rep->hbm_status = got[0] ? HBM_FAILED : HBM_OK;
@@ -410,7 +460,88 @@ extern "C" int egpu_selftest(int device, const egpu_selftest_params* p,
     }
   }
   rep->cus_seen = n_cus;
-  return run_hbm(p, res, rep);
+  const bool hbm_inject = p->inject_kind == INJECT_HBM;
+  const HbmCorruption corrupt = {&p->inject_arg, hbm_inject ? 1 : 0, 0};
+  return run_hbm(p->hbm_bytes, p->seed, corrupt, res, rep);
+}
+
+// Test-only: the memory check alone, with up to EGPU_SELFTEST_MAX_CORRUPT
+// words corrupted (bit 0 flipped) after the write of `corrupt_pass`. Fills
+// the hbm_* fields of the report. The grid is the production one.
+extern "C" int egpu_selftest_hbm(int device, uint64_t hbm_bytes, uint32_t seed,
+                                 const uint64_t* corrupt, int n_corrupt, int corrupt_pass,
+                                 egpu_selftest_report* rep) {
+  if (rep == nullptr) EGPU_BAD_ARG("selftest_hbm: report is null");
+  if (device < 0) EGPU_BAD_ARG("selftest_hbm: device %d is negative", device);
+  if (int rc = validate_hbm_bytes("selftest_hbm", hbm_bytes, EGPU_SELFTEST_MAX_HBM)) return rc;
+  if (n_corrupt < 0 || n_corrupt > EGPU_SELFTEST_MAX_CORRUPT)
+    EGPU_BAD_ARG("selftest_hbm: %d corrupt offsets, at most %d", n_corrupt,
+                 EGPU_SELFTEST_MAX_CORRUPT);
+  if (n_corrupt > 0 && corrupt == nullptr) EGPU_BAD_ARG("selftest_hbm: corrupt is null");
+  if (corrupt_pass != 0 && corrupt_pass != 1)
+    EGPU_BAD_ARG("selftest_hbm: corrupt_pass %d is neither 0 nor 1", corrupt_pass);
+  for (int c = 0; c < n_corrupt; ++c) {
+    if (corrupt[c] % 4 != 0 || corrupt[c] >= hbm_bytes)
+      EGPU_BAD_ARG("selftest_hbm: corrupt offset %llu is not a word offset inside hbm_bytes",
+                   (unsigned long long)corrupt[c]);
+    for (int d = 0; d < c; ++d)
+      if (corrupt[d] == corrupt[c])
+        EGPU_BAD_ARG("selftest_hbm: corrupt offset %llu is given twice",
+                     (unsigned long long)corrupt[c]);
+  }
+  *rep = egpu_selftest_report{};
+  rep->version = EGPU_SELFTEST_VERSION;
+  EGPU_CHECK(hipSetDevice(device));
+  Resources res;
+  return run_hbm(hbm_bytes, seed, HbmCorruption{corrupt, n_corrupt, corrupt_pass}, res, rep);
+}
+
+// Test-only: what the write launch of `pass` stores. Runs it with the
+// production grid over a buffer preset to 0xA5 bytes (a word the kernel
+// skipped shows as 0xA5A5A5A5) and copies the hbm_bytes back to `out`.
+extern "C" int egpu_selftest_hbm_image(int device, uint64_t hbm_bytes, uint32_t seed, int pass,
+                                       void* out) {
+  if (out == nullptr) EGPU_BAD_ARG("selftest_hbm_image: out is null");
+  if (device < 0) EGPU_BAD_ARG("selftest_hbm_image: device %d is negative", device);
+  if (int rc = validate_hbm_bytes("selftest_hbm_image", hbm_bytes, EGPU_SELFTEST_MAX_IMAGE))
+    return rc;
+  if (hbm_bytes == 0) EGPU_BAD_ARG("selftest_hbm_image: hbm_bytes is 0");
+  if (pass != 0 && pass != 1) EGPU_BAD_ARG("selftest_hbm_image: pass %d is neither 0 nor 1", pass);
+  EGPU_CHECK(hipSetDevice(device));
+  Resources res;
+  EGPU_CHECK(hipMalloc(&res.dev[1], hbm_bytes));
+  EGPU_CHECK(hipMemset(res.dev[1], 0xA5, hbm_bytes));
+  const uint64_t n16 = hbm_bytes / 16;
+  hipLaunchKernelGGL(hbm_pattern_kernel, dim3(hbm_grid(n16)), dim3(256), 0, 0,
+                     (uint4*)res.dev[1], n16, seed, pass ? 0xffffffffu : 0u, 0, nullptr, nullptr);
+  EGPU_CHECK(hipGetLastError());
+  EGPU_CHECK(hipDeviceSynchronize());
+  EGPU_CHECK(hipMemcpy(out, res.dev[1], hbm_bytes, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// The memory-path pattern of elements first .. first+n, four words each, and
+// the LDS march pattern of words first .. first+n, as the kernels generate
+// them. Neither touches a HIP API.
+extern "C" int egpu_selftest_hbm_words(uint64_t first, uint64_t n, uint32_t seed, uint32_t* out) {
+  if (out == nullptr) EGPU_BAD_ARG("selftest_hbm_words: out is null");
+  const uint64_t max16 = EGPU_SELFTEST_MAX_HBM / 16;
+  if (first > max16 || n > max16 - first)
+    EGPU_BAD_ARG("selftest_hbm_words: elements %llu .. +%llu pass the %llu of the largest buffer",
+                 (unsigned long long)first, (unsigned long long)n, (unsigned long long)max16);
+  for (uint64_t e = 0; e < n; ++e)
+    for (int k = 0; k < 4; ++k) out[4 * e + k] = egpu_st::hbm_word(first + e, k, seed);
+  return 0;
+}
+
+extern "C" int egpu_selftest_lds_words(uint32_t first, uint32_t n, uint32_t seed, uint32_t* out) {
+  if (out == nullptr) EGPU_BAD_ARG("selftest_lds_words: out is null");
+  const uint32_t max_words = EGPU_SELFTEST_MAX_LDS / 4;
+  if (first > max_words || n > max_words - first)
+    EGPU_BAD_ARG("selftest_lds_words: words %u .. +%u pass the %u of the largest LDS", first, n,
+                 max_words);
+  for (uint32_t w = 0; w < n; ++w) out[w] = egpu_st::lds_word(first + w, seed);
+  return 0;
 }
 
 // The raw records of one compute run, RECORD_WORDS words per wave:

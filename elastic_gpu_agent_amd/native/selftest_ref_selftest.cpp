@@ -3,9 +3,10 @@
 // directly (libegpu_kernels.so itself is never run under a sanitizer).
 //
 // Checks: determinism, the bound on `rounds`, that the 64 patterns give 64
-// distinct records, the exactness bound of the MFMA accumulator, and a few
+// distinct records, the exactness bound of the MFMA accumulator, a few
 // literal signatures (the FMA literals are what std::fmaf gives: this file is
-// compiled without any GPU toolchain in the way).
+// compiled without any GPU toolchain in the way), and literal words and
+// distinctness of the LDS-march and memory-path patterns.
 //
 // Build + run: python -m elastic_gpu_agent_amd.native.build_fuzz --selftest
 #include <cstdint>
@@ -127,6 +128,44 @@ void test_literals() {
   CHECK(one == 0x000e5920u, "single fmaf step");
 }
 
+// The storage patterns: literals from the numpy oracle of
+// tests/test_selftest_ref.py (the same ones it asserts), and what follows from
+// mix32 being a bijection.
+void test_storage_patterns() {
+  using egpu_st::hbm_word;
+  using egpu_st::lds_word;
+  const uint32_t zero[4] = {0x00000000u, 0x688990c0u, 0xd1132181u, 0x53f1e9ddu};
+  const uint32_t five[4] = {0xb0f32e7bu, 0x4ed33942u, 0x7c2f3b42u, 0xb550fdfcu};
+  // elements 2^30 - 1 and 2^30: the word index passes 2^32 between them
+  const uint32_t split[8] = {0x256ed7e7u, 0x9c5bff77u, 0x3ea41702u, 0xcd705cb3u,
+                             0x1053218au, 0x2c99bdf2u, 0x0bc690c9u, 0xcc3419c6u};
+  const uint32_t last[4] = {0x0edcffdau, 0x1f22948eu, 0x005cd305u, 0x123a4a88u};
+  for (int k = 0; k < 4; ++k) {
+    CHECK(hbm_word(0, k, 0) == zero[k], "element 0, seed 0");
+    CHECK(hbm_word(5, k, 0x5eed1234u) == five[k], "element 5");
+    CHECK(hbm_word((1ull << 30) - 1, k, 0x5eed1234u) == split[k], "element 2^30 - 1");
+    CHECK(hbm_word(1ull << 30, k, 0x5eed1234u) == split[4 + k], "element 2^30");
+    CHECK(hbm_word((1ull << 32) - 1, k, 0xffffffffu) == last[k], "last element of 64 GiB");
+  }
+  CHECK(lds_word(0, 0) == 0x00000000u && lds_word(1, 0) == 0x01fce552u, "LDS words 0, 1");
+  CHECK(lds_word(255, 0x5eed1234u) == 0xa9c4cdc2u && lds_word(256, 0x5eed1234u) == 0x9bad4bafu &&
+            lds_word(257, 0x5eed1234u) == 0x5a47cec1u,
+        "LDS words 255..257");
+  CHECK(lds_word(EGPU_SELFTEST_MAX_LDS / 4 - 1, 0xffffffffu) == 0xc272bd73u, "last LDS word");
+
+  for (uint32_t seed : {0u, 0x5eed1234u, 0xffffffffu}) {
+    std::set<uint32_t> hbm, lds;
+    const uint64_t n16 = ((1u << 20) + 16) / 16;  // the scratch buffer of the GPU tests
+    for (uint64_t i = 0; i < n16; ++i)
+      for (int k = 0; k < 4; ++k) hbm.insert(hbm_word(i, k, seed));
+    CHECK(hbm.size() == 4 * n16, "every word of the buffer distinct");
+    for (uint32_t w = 0; w < EGPU_SELFTEST_MAX_LDS / 4; ++w) lds.insert(lds_word(w, seed));
+    CHECK(lds.size() == EGPU_SELFTEST_MAX_LDS / 4, "every word of a full-LDS march distinct");
+    for (int k = 0; k < 4; ++k)
+      CHECK(hbm_word(1ull << 30, k, seed) != hbm_word(0, k, seed), "2^30 does not alias 0");
+  }
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -143,6 +182,7 @@ int main(int argc, char** argv) {
   test_patterns_distinct();
   test_lane_swap_changes_signature();
   test_literals();
+  test_storage_patterns();
   if (failures) {
     fprintf(stderr, "selftest_ref: %d check(s) failed\n", failures);
     return 1;

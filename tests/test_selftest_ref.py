@@ -129,6 +129,108 @@ def _mfma_sig(seed, pattern, rounds):
     return tile_signature(d)
 
 
+def hbm_words(first, n, seed):
+    """Memory-path pattern, from its definition: element i (16 bytes) holds
+    words k = 0..3, word = mix32(low32(4*i + k) + mix32(seed + (i >> 30))).
+    The 34-bit word index of the 64 GiB maximum is split: its low 32 bits are
+    mixed directly, its top bits (i >> 30) choose the base. Returns the 4*n
+    words of elements first .. first+n in memory order. (Also used by the GPU
+    tests, as is lds_words.)"""
+    i = np.arange(first, first + n, dtype=np.uint64)
+    base = _mix32(U(seed) + (i >> np.uint64(30)).astype(U))
+    index = i[:, None] * np.uint64(4) + np.arange(4, dtype=np.uint64)[None, :]
+    low = (index & np.uint64(0xFFFFFFFF)).astype(U)
+    return _mix32(low + base[:, None]).reshape(-1)
+
+
+def lds_words(first, n, seed):
+    """LDS march pattern: word w holds mix32(w * 0x9E3779B9 + seed)."""
+    w = np.arange(first, first + n, dtype=np.uint64).astype(U)
+    return _mix32(w * U(0x9E3779B9) + U(seed))
+
+
+PATTERN_SEEDS = [0, 0x5EED1234, 0xFFFFFFFF]
+# (first element, count): the start of a buffer; the elements around 2^30,
+# where the word index passes 2^32; the last elements of the 64 GiB maximum
+HBM_RANGES = [(0, 4096), ((1 << 30) - 2, 4), ((1 << 32) - 4, 4)]
+TEST_BUFFER_WORDS = ((1 << 20) + 16) // 4  # the scratch buffer of the GPU tests
+FULL_LDS_WORDS = probes.SELFTEST_MAX_LDS // 4
+
+
+@pytest.mark.parametrize("seed", PATTERN_SEEDS)
+@pytest.mark.parametrize("first, n", HBM_RANGES)
+def test_hbm_pattern_matches_numpy_oracle(seed, first, n):
+    got = np.array(probes.selftest_hbm_words(first, n, seed), dtype=U)
+    assert got.shape == (4 * n,)
+    assert np.array_equal(got, hbm_words(first, n, seed))
+
+
+@pytest.mark.parametrize("seed", PATTERN_SEEDS)
+def test_lds_pattern_matches_numpy_oracle(seed):
+    got = np.array(probes.selftest_lds_words(0, FULL_LDS_WORDS, seed), dtype=U)
+    assert np.array_equal(got, lds_words(0, FULL_LDS_WORDS, seed))
+    # a range that does not start at word 0
+    got = probes.selftest_lds_words(FULL_LDS_WORDS - 3, 3, seed)
+    assert got == lds_words(FULL_LDS_WORDS - 3, 3, seed).tolist()
+
+
+HBM_LITERAL_5 = [0xB0F32E7B, 0x4ED33942, 0x7C2F3B42, 0xB550FDFC]
+HBM_LITERAL_2_30 = [0x256ED7E7, 0x9C5BFF77, 0x3EA41702, 0xCD705CB3,
+                    0x1053218A, 0x2C99BDF2, 0x0BC690C9, 0xCC3419C6]
+HBM_LITERAL_LAST = [0x0EDCFFDA, 0x1F22948E, 0x005CD305, 0x123A4A88]
+LDS_LITERAL_255 = [0xA9C4CDC2, 0x9BAD4BAF, 0x5A47CEC1]
+LDS_LITERAL_LAST = [0xC272BD73]
+
+
+def test_pattern_literals():
+    """Values taken from the oracle above when it was written;
+    native/selftest_ref_selftest.cpp checks the same literals against the
+    header in a plain C++ build."""
+    for words in (probes.selftest_hbm_words, lambda *a: hbm_words(*a).tolist()):
+        assert words(0, 1, 0) == [0x00000000, 0x688990C0, 0xD1132181, 0x53F1E9DD]
+        assert words(5, 1, 0x5EED1234) == HBM_LITERAL_5
+        assert words((1 << 30) - 1, 2, 0x5EED1234) == HBM_LITERAL_2_30
+        assert words((1 << 32) - 1, 1, 0xFFFFFFFF) == HBM_LITERAL_LAST
+    for words in (probes.selftest_lds_words, lambda *a: lds_words(*a).tolist()):
+        assert words(0, 2, 0) == [0x00000000, 0x01FCE552]
+        assert words(255, 3, 0x5EED1234) == LDS_LITERAL_255
+        assert words(40959, 1, 0xFFFFFFFF) == LDS_LITERAL_LAST
+
+
+@pytest.mark.parametrize("seed", PATTERN_SEEDS)
+def test_pattern_words_are_distinct(seed):
+    """mix32 is a bijection of the 32-bit words and so is adding a constant
+    or multiplying by an odd one, hence two addresses of one buffer never hold
+    the same word: a write that lands on the wrong address line, at any
+    distance, is a miscompare."""
+    hbm = np.array(probes.selftest_hbm_words(0, TEST_BUFFER_WORDS // 4, seed), dtype=U)
+    assert hbm.size == TEST_BUFFER_WORDS and np.unique(hbm).size == hbm.size
+    distance = 1
+    while distance < hbm.size:  # follows from the line above; kept explicit
+        assert not (hbm[distance:] == hbm[:-distance]).any(), distance
+        distance *= 2
+    lds = np.array(probes.selftest_lds_words(0, FULL_LDS_WORDS, seed), dtype=U)
+    assert lds.size == 40960 and np.unique(lds).size == lds.size
+    # beyond 2^30 elements the low index repeats and only the base differs
+    far = probes.selftest_hbm_words(1 << 30, 1, seed)
+    assert all(a != b for a, b in zip(far, hbm[:4].tolist()))
+
+
+@pytest.mark.parametrize(
+    "call, needle",
+    [
+        (lambda: probes.selftest_hbm_words((1 << 32) - 1, 2), "elements"),
+        (lambda: probes.selftest_hbm_words((1 << 32) + 1, 0), "elements"),
+        (lambda: probes.selftest_lds_words(40959, 2), "words"),
+        (lambda: probes.selftest_lds_words(40961, 0), "words"),
+    ],
+)
+def test_pattern_exports_reject_ranges_past_the_maximum(call, needle):
+    with pytest.raises(probes.ProbeError, match=needle) as ei:
+        call()
+    assert "rc=-1" in str(ei.value)
+
+
 @pytest.mark.parametrize("seed", [0, 0x1234ABCD])
 @pytest.mark.parametrize("rounds", [1, 2, 5])
 def test_reference_matches_numpy_oracle(seed, rounds):
@@ -185,6 +287,15 @@ def test_rounds_bound_keeps_accumulator_exact():
         (dict(lds_bytes=32770), "lds_bytes"),
         (dict(_inject=("mfma", 17), blocks=17), "inject_arg"),
         (dict(_inject=("hbm", 4098)), "inject_arg"),
+        # the placed LDS injection: a word outside lds_bytes, a pass that is
+        # neither the pattern nor the complement
+        (dict(_inject=("lds", 0, 256, 0), lds_bytes=1024), "inject_sub word"),
+        (dict(_inject=("lds", 0, 257, 1), lds_bytes=1028), "inject_sub word"),
+        (dict(_inject=("lds", 0, 8192, 0), lds_bytes=32768), "inject_sub word"),
+        (dict(_inject=("lds", 0, 40960, 1), lds_bytes=163840), "inject_sub word"),
+        (dict(_inject=("lds", 0, 0, 2)), "inject_sub .* pass"),
+        (dict(_inject=("lds", 0, 0, 127)), "inject_sub .* pass"),
+        (dict(_inject=("lds", 3, 0, 0), blocks=3), "inject_arg"),
     ],
 )
 def test_bad_arguments_fail_before_any_gpu_call(kwargs, needle):
@@ -192,6 +303,60 @@ def test_bad_arguments_fail_before_any_gpu_call(kwargs, needle):
     or without a GPU, and nothing is launched."""
     with pytest.raises(probes.ProbeError, match=needle) as ei:
         probes.selftest(0, **kwargs)
+    assert "rc=-1" in str(ei.value)
+
+
+def test_records_validate_the_placed_injection_too():
+    with pytest.raises(probes.ProbeError, match="inject_sub word") as ei:
+        probes.selftest_records(0, blocks=3, lds_bytes=1024, _inject=("lds", 1, 256, 1))
+    assert "rc=-1" in str(ei.value)
+
+
+@pytest.mark.parametrize("inject", [("mfma", 0, 0, 0), ("lds", 0, 1 << 24, 0),
+                                    ("lds", 0, 0, 128), ("lds", 0, -1, 0), ("lds", 0, 5)])
+def test_placed_injection_without_an_encoding_is_a_value_error(inject):
+    with pytest.raises(ValueError):
+        probes.selftest(0, _inject=inject)
+
+
+BUF = (1 << 20) + 16
+
+
+@pytest.mark.parametrize(
+    "kwargs, needle",
+    [
+        (dict(corrupt=range(0, 4 * 65, 4)), "65 corrupt offsets"),
+        (dict(corrupt=[4098]), "offset 4098"),
+        (dict(corrupt=[BUF]), f"offset {BUF}"),
+        (dict(corrupt=[8, 4096, 8]), "offset 8 is given twice"),
+        (dict(corrupt=[0], corrupt_pass=2), "corrupt_pass"),
+        (dict(corrupt=[0], corrupt_pass=-1), "corrupt_pass"),
+        (dict(hbm_bytes=BUF + 8), "hbm_bytes"),
+        (dict(hbm_bytes=0, corrupt=[0]), "offset 0"),
+    ],
+)
+def test_memory_check_entry_rejects_bad_arguments_before_any_gpu_call(kwargs, needle):
+    kwargs = {"hbm_bytes": BUF, **kwargs}
+    kwargs["corrupt"] = list(kwargs.get("corrupt", ()))
+    with pytest.raises(probes.ProbeError, match=needle) as ei:
+        probes.selftest_hbm(0, seed=1, **kwargs)
+    assert "rc=-1" in str(ei.value)
+
+
+@pytest.mark.parametrize(
+    "hbm_bytes, march_pass, needle",
+    [
+        (probes.SELFTEST_MAX_IMAGE + 16, 0, "hbm_bytes"),
+        (0, 0, "hbm_bytes"),
+        (24, 1, "hbm_bytes"),
+        (16, 2, "pass"),
+        (16, -1, "pass"),
+    ],
+)
+def test_memory_image_rejects_bad_arguments_before_any_gpu_call(hbm_bytes, march_pass, needle):
+    assert probes.SELFTEST_MAX_IMAGE == (16 << 20) + 16
+    with pytest.raises(probes.ProbeError, match=needle) as ei:
+        probes.selftest_hbm_image(0, hbm_bytes, 1, march_pass)
     assert "rc=-1" in str(ei.value)
 
 

@@ -51,6 +51,10 @@ def main(argv=None) -> int:
     parser.add_argument("--gpu-selftest-matrix", action="store_true",
                         help="each self-test probe also runs the matrix sweep: "
                              "the FP8, FP6, FP4, INT8, F16 and 16x16 MFMA paths")
+    parser.add_argument("--gpu-selftest-move", action="store_true",
+                        help="each self-test probe also runs the move sweep: "
+                             "direct-to-LDS loads, 128-bit and transposing LDS "
+                             "reads, bpermute, permlane swaps and DPP")
     parser.add_argument("--recordFormat", choices=["runs", "list"], default="runs",
                         help="how the state DB holds a large consecutive device "
                              "set: as ID runs, or as the literal list that "
@@ -114,6 +118,7 @@ def main(argv=None) -> int:
         selftest_seconds=args.gpu_selftest_seconds,
         selftest_timeout=args.gpu_selftest_timeout,
         selftest_matrix=args.gpu_selftest_matrix,
+        selftest_move=args.gpu_selftest_move,
         record_format=args.recordFormat,
         hash_memo_entries=args.hashMemoEntries,
     )

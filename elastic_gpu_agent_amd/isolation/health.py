@@ -24,7 +24,10 @@ Policy:
   the memory) is not a failure;
 - with ``matrix`` on (off by default) the child also runs the matrix sweep
   (``probes.mx_selftest``: FP8, FP6, FP4, INT8, F16 and 16x16 MFMA paths) and
-  its miscompares count like any other.
+  its miscompares count like any other;
+- with ``move`` on (off by default) the child also runs the move sweep
+  (``probes.move_selftest``: direct-to-LDS loads, wide and transposing LDS
+  reads, cross-lane moves), judged the same way.
 
 The agent process itself never initialises HIP: every probe is a fresh child
 started with ``subprocess``, without ``HSA_TOOLS_LIB`` in its environment, and
@@ -74,17 +77,24 @@ FULL_PROBE = {"blocks": 1024, "rounds": 256, "lds_bytes": 163840, "hbm_bytes": 1
 # multiply-adds, so rounds is small (profiles/selftest.md).
 PERIODIC_MATRIX = {"blocks": 1024, "rounds": 8}
 FULL_MATRIX = {"blocks": 1024, "rounds": 64}
+# Move sweep (probes.move_selftest), run last when the child gets --move.
+# Rounds come in complement pairs, so they are even. Measured in
+# profiles/selftest.md: the sweep adds 0.007 s (periodic) and 0.018 s (full)
+# to the child's wall time.
+PERIODIC_MOVE = {"blocks": 1024, "rounds": 4}
+FULL_MOVE = {"blocks": 1024, "rounds": 16}
 
 # test-only: EGPU_SELFTEST_INJECT=<kind>[:arg] in the CHILD's environment
 # simulates a miscompare (kind int|fma|mfma|lds with a workgroup index, or hbm
 # with a byte offset; or one of probes.MX_KINDS with a workgroup index, which
-# corrupts that kind of the matrix sweep)
+# corrupts that kind of the matrix sweep; or one of probes.MOVE_KINDS, likewise
+# for the move sweep)
 INJECT_ENV = "EGPU_SELFTEST_INJECT"
 
 _REPORT_KEYS = (
     "waves_run", "cus_seen", "bad_waves", "bad_kind_names", "n_bad_cus", "bad_cus",
     "lds_bytes", "hbm_status", "hbm_bytes_checked", "hbm_miscompares",
-    "hbm_first_bad_offset", "kernel_ms", "hbm_ms", "matrix",
+    "hbm_first_bad_offset", "kernel_ms", "hbm_ms", "matrix", "move",
 )
 
 
@@ -139,15 +149,17 @@ def report_failures(report: dict) -> List[str]:
     if report.get("hbm_miscompares", 0) or report.get("hbm_status") == "failed":
         why.append(f"{report.get('hbm_miscompares')} memory miscompare(s), first at byte "
                    f"{report.get('hbm_first_bad_offset')}")
-    matrix = report.get("matrix")
-    if isinstance(matrix, dict):
-        if matrix.get("bad_waves", 0):
-            kinds = ",".join(matrix.get("bad_kind_names") or []) or "?"
-            why.append(f"matrix: {matrix['bad_waves']} bad wave(s) [{kinds}] on "
-                       f"{matrix.get('n_bad_cus', '?')} CU(s)")
-        blocks = matrix.get("blocks")
-        if blocks is not None and matrix.get("waves_run") != 4 * blocks:
-            why.append(f"matrix: {matrix.get('waves_run')} of {4 * blocks} waves reported")
+    for name in ("matrix", "move"):
+        sweep = report.get(name)
+        if not isinstance(sweep, dict):
+            continue
+        if sweep.get("bad_waves", 0):
+            kinds = ",".join(sweep.get("bad_kind_names") or []) or "?"
+            why.append(f"{name}: {sweep['bad_waves']} bad wave(s) [{kinds}] on "
+                       f"{sweep.get('n_bad_cus', '?')} CU(s)")
+        blocks = sweep.get("blocks")
+        if blocks is not None and sweep.get("waves_run") != 4 * blocks:
+            why.append(f"{name}: {sweep.get('waves_run')} of {4 * blocks} waves reported")
     return why
 
 
@@ -192,18 +204,21 @@ def apply_result(storage, gpu_index: int, result: dict, fail_threshold: int = 2,
 
 # ---------------------------------------------------------------- runner
 
-def _probe_argv(index: int, full: bool, matrix: bool = False) -> List[str]:
+def _probe_argv(index: int, full: bool, matrix: bool = False, move: bool = False) -> List[str]:
     argv = [sys.executable, "-m", "elastic_gpu_agent_amd.isolation.health",
             "--probe", str(index)]
     if full:
         argv.append("--full")
     if matrix:
         argv.append("--matrix")
+    if move:
+        argv.append("--move")
     return argv
 
 
 def subprocess_runner(index: int, timeout: float, full: bool = False,
-                      _argv: Optional[List[str]] = None, matrix: bool = False) -> dict:
+                      _argv: Optional[List[str]] = None, matrix: bool = False,
+                      move: bool = False) -> dict:
     """Runs the probe of GPU ``index`` in a fresh child and maps what happened
     to a result: {"outcome", "reason", "report", "wall_s"}. The last line of
     the child's stdout must be one JSON object."""
@@ -212,7 +227,7 @@ def subprocess_runner(index: int, timeout: float, full: bool = False,
     root = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     env["PYTHONPATH"] = os.pathsep.join(p for p in (root, env.get("PYTHONPATH")) if p)
     t0 = time.monotonic()
-    proc = subprocess.Popen(_argv or _probe_argv(index, full, matrix), env=env,
+    proc = subprocess.Popen(_argv or _probe_argv(index, full, matrix, move), env=env,
                             stdin=subprocess.DEVNULL, stdout=subprocess.PIPE,
                             stderr=subprocess.PIPE, text=True)
 
@@ -254,7 +269,7 @@ class HealthMonitor:
                  interval: float = 600.0, fail_threshold: int = 2,
                  on_change: Optional[Callable[[], None]] = None, event_sink=None,
                  limits=None, timeout: float = DEFAULT_TIMEOUT_SECONDS,
-                 matrix: bool = False):
+                 matrix: bool = False, move: bool = False):
         self.storage = storage
         self.operator = operator
         self.runner = runner
@@ -265,6 +280,7 @@ class HealthMonitor:
         self.limits = limits
         self.timeout = timeout
         self.matrix = matrix
+        self.move = move
         self._stop = threading.Event()
         self._probe_lock = threading.Lock()  # never two probes at once
         self._thread: Optional[threading.Thread] = None
@@ -284,10 +300,10 @@ class HealthMonitor:
                     continue
                 t0 = time.perf_counter()
                 try:
-                    # the keyword only when set: a runner written before the
-                    # matrix sweep takes two arguments
-                    result = (self.runner(idx, self.timeout, matrix=True) if self.matrix
-                              else self.runner(idx, self.timeout))
+                    # a keyword only when set: a runner written before the
+                    # sweeps takes two arguments
+                    sweeps = {k: True for k in ("matrix", "move") if getattr(self, k)}
+                    result = self.runner(idx, self.timeout, **sweeps)
                 except Exception as e:  # a runner that cannot start a child
                     result = {"outcome": OUTCOME_CRASH, "reason": f"runner: {e}"}
                 GLOBAL_METRICS.recorder(GPU_SELFTEST).observe(time.perf_counter() - t0)
@@ -363,23 +379,30 @@ def _probe_main(argv: List[str]) -> int:
     p.add_argument("--probe", type=int, required=True, metavar="GPU")
     p.add_argument("--full", action="store_true")
     p.add_argument("--matrix", action="store_true")
+    p.add_argument("--move", action="store_true")
     args = p.parse_args(argv)
     from . import probes
 
     sizes = dict(FULL_PROBE if args.full else PERIODIC_PROBE)
     inject = os.environ.get(INJECT_ENV)
     inject = _parse_inject(inject) if inject else None
-    # a matrix kind's name selects the sweep, any other name the probe above
-    # (without --matrix there is no sweep to corrupt and it does nothing)
+    # a sweep kind's name selects that sweep, any other name the probe above
+    # (without the sweep's flag there is nothing to corrupt and it does nothing)
     mx_inject = inject if inject and inject[0] in probes.MX_KINDS else None
+    move_inject = inject if inject and inject[0] in probes.MOVE_KINDS else None
     seed = int(time.time()) & 0xFFFFFFFF
     report = probes.selftest(args.probe, seed=seed,
-                             _inject=None if mx_inject else inject, **sizes)
+                             _inject=None if mx_inject or move_inject else inject, **sizes)
     report.update(gpu=args.probe, blocks=sizes["blocks"], rounds=sizes["rounds"], seed=seed)
     if args.matrix:
         mx_sizes = dict(FULL_MATRIX if args.full else PERIODIC_MATRIX)
         report["matrix"] = dict(
             probes.mx_selftest(args.probe, seed=seed, _inject=mx_inject, **mx_sizes), **mx_sizes)
+    if args.move:
+        mv_sizes = dict(FULL_MOVE if args.full else PERIODIC_MOVE)
+        report["move"] = dict(
+            probes.move_selftest(args.probe, seed=seed, _inject=move_inject, **mv_sizes),
+            **mv_sizes)
     print(json.dumps(report), flush=True)
     return 0
 

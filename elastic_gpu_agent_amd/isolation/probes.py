@@ -76,6 +76,21 @@ def _lib():
         lib.egpu_mxtest_lane_regs.argtypes = [
             ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_int,
         ] + [ctypes.POINTER(ctypes.c_uint32)] * 4
+        lib.egpu_movetest.argtypes = [
+            ctypes.c_int, ctypes.POINTER(_MoveParams), ctypes.POINTER(_MoveReport)
+        ]
+        lib.egpu_movetest_records.argtypes = [
+            ctypes.c_int, ctypes.POINTER(_MoveParams),
+            ctypes.POINTER(ctypes.c_uint32), ctypes.c_int,
+        ]
+        lib.egpu_movetest_expected.argtypes = [
+            ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(ctypes.c_uint32)
+        ]
+        lib.egpu_movetest_tile.argtypes = [
+            ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_int,
+            ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32),
+        ]
+        lib.egpu_movetest_lane_map.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_int32)]
         lib.egpu_selftest_hbm.argtypes = [
             ctypes.c_int, ctypes.c_uint64, ctypes.c_uint32,
             ctypes.POINTER(ctypes.c_uint64), ctypes.c_int, ctypes.c_int,
@@ -451,3 +466,107 @@ def mx_selftest_lane_regs(kind: str, pattern: int = 0, seed: int = 0, round: int
                                         round, a, b, sa, sb), "egpu_mxtest_lane_regs")
     return ([list(a[8 * l: 8 * l + 8]) for l in range(64)],
             [list(b[8 * l: 8 * l + 8]) for l in range(64)], list(sa), list(sb))
+
+
+# ---------------------------------------------------------------- move sweep
+
+MOVE_MAX_ROUNDS = 256
+MOVE_PATTERNS = 16
+# bad_kinds bits, in the order of the record's signatures
+MOVE_KINDS = {"g2l16": 1, "g2l4": 2, "b128": 4, "tr16": 8, "tr8": 16, "tr6": 32, "tr4": 64,
+              "bperm": 128, "swap": 256, "dpp": 512}
+# kind -> (element bits, elements a lane receives per tile through the lane
+# map, source elements the map covers). A tile is 256 words; see
+# move_selftest_lane_map for how elements are numbered.
+MOVE_GEOMETRY = {"g2l16": (32, 4, 256), "g2l4": (32, 4, 256), "b128": (32, 4, 256),
+                 "tr16": (16, 8, 512), "tr8": (8, 16, 1024), "tr6": (6, 16, 1024),
+                 "tr4": (4, 32, 2048), "bperm": (32, 4, 256), "swap": (32, 4, 256),
+                 "dpp": (32, 2, 128)}
+_MOVE_INDEX = {name: i for i, name in enumerate(MOVE_KINDS)}
+
+_MoveParams = _MxParams  # {blocks, rounds, seed, inject_kind, inject_block}
+_MoveReport = _MxReport
+
+
+def _move_params(blocks, rounds, seed, inject) -> _MoveParams:
+    kind, block = -1, -1
+    if inject is not None:
+        if inject[0] not in _MOVE_INDEX:
+            raise ValueError(f"unknown move kind {inject[0]!r}")
+        kind, block = _MOVE_INDEX[inject[0]], inject[1]
+    return _MoveParams(blocks, rounds, seed & 0xFFFFFFFF, kind, block)
+
+
+def move_selftest(device: int = 0, blocks: int = 1024, rounds: int = 4, seed: int = 0,
+                  _inject=None) -> dict:
+    """Move sweep: every wave of a `blocks`-workgroup grid moves `rounds` slabs
+    through every kind of MOVE_KINDS (direct global-to-LDS loads, 128-bit LDS
+    accesses, the transposing LDS reads, bpermute/permute, the permlane swaps,
+    DPP) and its fold of what the lanes received is compared with the host
+    reference. Bad arguments raise ProbeError before any HIP call. `_inject` =
+    (kind name, workgroup) simulates a miscompare (tests only)."""
+    params = _move_params(blocks, rounds, seed, _inject)
+    rep = _MoveReport()
+    _check(_lib().egpu_movetest(device, ctypes.byref(params), ctypes.byref(rep)),
+           "egpu_movetest")
+    return {
+        "version": rep.version,
+        "waves_run": rep.waves_run,
+        "cus_seen": rep.cus_seen,
+        "bad_waves": rep.bad_waves,
+        "bad_kinds": rep.bad_kinds,
+        "bad_kind_names": [k for k, bit in MOVE_KINDS.items() if rep.bad_kinds & bit],
+        "n_bad_cus": rep.n_bad_cus,
+        "bad_cus": list(rep.bad_cus[: rep.n_bad_cus]),
+        "kernel_ms": rep.kernel_ms,
+    }
+
+
+def move_selftest_records(device: int = 0, blocks: int = 4, rounds: int = 4,
+                          seed: int = 0) -> List[tuple]:
+    """The raw per-wave records of one sweep, in wave order:
+    (cu_id, (signature of every kind, in MOVE_KINDS order))."""
+    params = _move_params(blocks, rounds, seed, None)
+    n = blocks * 4 if blocks > 0 else 0
+    w = 1 + len(MOVE_KINDS)
+    buf = (ctypes.c_uint32 * max(1, n * w))()
+    _check(_lib().egpu_movetest_records(device, ctypes.byref(params), buf, n),
+           "egpu_movetest_records")
+    return [(buf[w * i], tuple(buf[w * i + 1: w * i + w])) for i in range(n)]
+
+
+def move_selftest_expected(seed: int = 0, rounds: int = 4) -> List[dict]:
+    """Host reference: for each of the 16 patterns, {kind name: signature}.
+    Runs no GPU code, so it works on a machine without one."""
+    n = len(MOVE_KINDS)
+    out = (ctypes.c_uint32 * (MOVE_PATTERNS * n))()
+    _check(_lib().egpu_movetest_expected(seed & 0xFFFFFFFF, rounds, out),
+           "egpu_movetest_expected")
+    return [dict(zip(MOVE_KINDS, out[n * p: n * p + n])) for p in range(MOVE_PATTERNS)]
+
+
+def move_selftest_tile(device: int = 0, kind: str = "tr16", pattern: int = 0, seed: int = 0,
+                       round: int = 0):
+    """One wave, one kind, one round, tile 0: (regs, src). regs is 64 lists of
+    the 4 register words the lane received (unused ones zero); src the 256
+    source words: the LDS tile, the global words of a direct-to-LDS load, or
+    for the lane kinds source register r of lane l at 64 * r + l."""
+    regs = (ctypes.c_uint32 * 256)()
+    src = (ctypes.c_uint32 * 256)()
+    _check(_lib().egpu_movetest_tile(device, _MOVE_INDEX.get(kind, -1), pattern,
+                                     seed & 0xFFFFFFFF, round, regs, src), "egpu_movetest_tile")
+    return [list(regs[4 * l: 4 * l + 4]) for l in range(64)], list(src)
+
+
+def move_selftest_lane_map(kind: str) -> List[List[int]]:
+    """Host only: for each of the 64 lanes, the source element index of every
+    element it receives (MOVE_GEOMETRY[kind][1] of them, element j at bit
+    j * bits of the lane's registers). Source elements are packed little-endian
+    in the tile, except tr6: element k is the 6 bits at bit 6 * (k % 16) of
+    the 16-byte row k // 16. bperm: the map of round 0. dpp: registers 0 and 1
+    only (2 and 3 are broadcasts)."""
+    elems = MOVE_GEOMETRY[kind][1] if kind in MOVE_GEOMETRY else 1
+    out = (ctypes.c_int32 * (64 * 32))()
+    _check(_lib().egpu_movetest_lane_map(_MOVE_INDEX.get(kind, -1), out),
+           "egpu_movetest_lane_map")
+    return [list(out[elems * l: elems * l + elems]) for l in range(64)]

@@ -45,6 +45,8 @@ class ManagerOptions:
     selftest_timeout: float = 10.0
     # each probe also runs the matrix sweep (probes.mx_selftest)
     selftest_matrix: bool = False
+    # each probe also runs the move sweep (probes.move_selftest)
+    selftest_move: bool = False
     # how the store's rows hold a large consecutive device set: "runs"
     # (ID runs) or "list" (the reference-format record; the way back for a
     # rollback to a build that cannot read runs)
@@ -211,6 +213,7 @@ class GPUManager:
             limits=self.config.limits,
             timeout=self.opts.selftest_timeout,
             matrix=self.opts.selftest_matrix,
+            move=self.opts.selftest_move,
         )
         self.health_monitor.start()
 

@@ -1,6 +1,6 @@
 """Build + (optionally) run the libFuzzer harness over the native parsers,
 and the stand-alone sanitizer self-tests of the device-set digest, of the
-ID-run codec the store uses, of the GPU self-test's host reference, of the
+ID-run codec the store uses, of the GPU self-test's host references, of the
 transport's HTTP/2 framing core, of the Allocate -> PreStart hash memo and of
 the native file effects of a bind.
 
@@ -12,6 +12,8 @@ Usage:
                                                                 # (general, then fixed-stride/radix),
                                                                 # then the ID-run codec,
                                                                 # then selftest_ref.h,
+                                                                # selftest_mx_ref.h and
+                                                                # selftest_move_ref.h,
                                                                 # then h2frame.h,
                                                                 # then the hash memo,
                                                                 # then bindfx.h
@@ -117,6 +119,14 @@ def build_mx_ref_selftest(out=None):
     return build_selftest(out, "selftest_mx_ref_selftest.cpp")
 
 
+def build_move_ref_selftest(out=None):
+    """selftest_move_ref_selftest.cpp: the host reference of the move sweep
+    (selftest_move_ref.h: generator, lane maps, fold, expected signatures; no
+    GPU code), built the same way."""
+    out = out or os.path.join(REPO, "bin", "egpu-selftest-move-ref-selftest")
+    return build_selftest(out, "selftest_move_ref_selftest.cpp")
+
+
 def build_h2frame_selftest(out=None):
     """h2frame_selftest.cpp: the transport's receive buffer, frame parser and
     header-block builders (h2frame.h, no Python) over a socketpair, built the
@@ -147,6 +157,7 @@ if __name__ == "__main__":
         rc = rc or subprocess.call([build_runs_selftest()])
         rc = rc or subprocess.call([build_ref_selftest()])
         rc = rc or subprocess.call([build_mx_ref_selftest()])
+        rc = rc or subprocess.call([build_move_ref_selftest()])
         rc = rc or subprocess.call([build_h2frame_selftest()])
         rc = rc or subprocess.call([build_hash_memo_selftest()])
         sys.exit(rc or subprocess.call([build_bindfx_selftest()]))

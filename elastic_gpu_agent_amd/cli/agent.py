@@ -55,6 +55,10 @@ def main(argv=None) -> int:
                         help="each self-test probe also runs the move sweep: "
                              "direct-to-LDS loads, 128-bit and transposing LDS "
                              "reads, bpermute, permlane swaps and DPP")
+    parser.add_argument("--gpu-selftest-cvt", action="store_true",
+                        help="each self-test probe also runs the conversion sweep: "
+                             "the block-scaled FP8, FP6 and FP4 quantise and "
+                             "dequantise instructions and the unscaled FP8 converts")
     parser.add_argument("--recordFormat", choices=["runs", "list"], default="runs",
                         help="how the state DB holds a large consecutive device "
                              "set: as ID runs, or as the literal list that "
@@ -119,6 +123,7 @@ def main(argv=None) -> int:
         selftest_timeout=args.gpu_selftest_timeout,
         selftest_matrix=args.gpu_selftest_matrix,
         selftest_move=args.gpu_selftest_move,
+        selftest_cvt=args.gpu_selftest_cvt,
         record_format=args.recordFormat,
         hash_memo_entries=args.hashMemoEntries,
     )

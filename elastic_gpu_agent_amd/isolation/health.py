@@ -27,7 +27,10 @@ Policy:
   its miscompares count like any other;
 - with ``move`` on (off by default) the child also runs the move sweep
   (``probes.move_selftest``: direct-to-LDS loads, wide and transposing LDS
-  reads, cross-lane moves), judged the same way.
+  reads, cross-lane moves), judged the same way;
+- with ``cvt`` on (off by default) the child also runs the conversion sweep
+  (``probes.cvt_selftest``: the block-scaled FP8, FP6 and FP4 quantise and
+  dequantise instructions and the unscaled FP8 converts), judged the same way.
 
 The agent process itself never initialises HIP: every probe is a fresh child
 started with ``subprocess``, without ``HSA_TOOLS_LIB`` in its environment, and
@@ -83,18 +86,24 @@ FULL_MATRIX = {"blocks": 1024, "rounds": 64}
 # to the child's wall time.
 PERIODIC_MOVE = {"blocks": 1024, "rounds": 4}
 FULL_MOVE = {"blocks": 1024, "rounds": 16}
+# Conversion sweep (probes.cvt_selftest), run last when the child gets --cvt.
+# Rounds come in complement pairs of the preserved bits, so they are even.
+# Measured in profiles/selftest.md: the sweep adds 0.032 s (periodic) and
+# 0.127 s (full) to the child's wall time, nearly all of it the host reference.
+PERIODIC_CVT = {"blocks": 1024, "rounds": 4}
+FULL_CVT = {"blocks": 1024, "rounds": 16}
 
 # test-only: EGPU_SELFTEST_INJECT=<kind>[:arg] in the CHILD's environment
 # simulates a miscompare (kind int|fma|mfma|lds with a workgroup index, or hbm
 # with a byte offset; or one of probes.MX_KINDS with a workgroup index, which
-# corrupts that kind of the matrix sweep; or one of probes.MOVE_KINDS, likewise
-# for the move sweep)
+# corrupts that kind of the matrix sweep; or one of probes.MOVE_KINDS or
+# probes.CVT_KINDS, likewise for the move and the conversion sweep)
 INJECT_ENV = "EGPU_SELFTEST_INJECT"
 
 _REPORT_KEYS = (
     "waves_run", "cus_seen", "bad_waves", "bad_kind_names", "n_bad_cus", "bad_cus",
     "lds_bytes", "hbm_status", "hbm_bytes_checked", "hbm_miscompares",
-    "hbm_first_bad_offset", "kernel_ms", "hbm_ms", "matrix", "move",
+    "hbm_first_bad_offset", "kernel_ms", "hbm_ms", "matrix", "move", "cvt",
 )
 
 
@@ -149,7 +158,7 @@ def report_failures(report: dict) -> List[str]:
     if report.get("hbm_miscompares", 0) or report.get("hbm_status") == "failed":
         why.append(f"{report.get('hbm_miscompares')} memory miscompare(s), first at byte "
                    f"{report.get('hbm_first_bad_offset')}")
-    for name in ("matrix", "move"):
+    for name in ("matrix", "move", "cvt"):
         sweep = report.get(name)
         if not isinstance(sweep, dict):
             continue
@@ -204,7 +213,8 @@ def apply_result(storage, gpu_index: int, result: dict, fail_threshold: int = 2,
 
 # ---------------------------------------------------------------- runner
 
-def _probe_argv(index: int, full: bool, matrix: bool = False, move: bool = False) -> List[str]:
+def _probe_argv(index: int, full: bool, matrix: bool = False, move: bool = False,
+                cvt: bool = False) -> List[str]:
     argv = [sys.executable, "-m", "elastic_gpu_agent_amd.isolation.health",
             "--probe", str(index)]
     if full:
@@ -213,12 +223,14 @@ def _probe_argv(index: int, full: bool, matrix: bool = False, move: bool = False
         argv.append("--matrix")
     if move:
         argv.append("--move")
+    if cvt:
+        argv.append("--cvt")
     return argv
 
 
 def subprocess_runner(index: int, timeout: float, full: bool = False,
                       _argv: Optional[List[str]] = None, matrix: bool = False,
-                      move: bool = False) -> dict:
+                      move: bool = False, cvt: bool = False) -> dict:
     """Runs the probe of GPU ``index`` in a fresh child and maps what happened
     to a result: {"outcome", "reason", "report", "wall_s"}. The last line of
     the child's stdout must be one JSON object."""
@@ -227,7 +239,7 @@ def subprocess_runner(index: int, timeout: float, full: bool = False,
     root = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     env["PYTHONPATH"] = os.pathsep.join(p for p in (root, env.get("PYTHONPATH")) if p)
     t0 = time.monotonic()
-    proc = subprocess.Popen(_argv or _probe_argv(index, full, matrix, move), env=env,
+    proc = subprocess.Popen(_argv or _probe_argv(index, full, matrix, move, cvt), env=env,
                             stdin=subprocess.DEVNULL, stdout=subprocess.PIPE,
                             stderr=subprocess.PIPE, text=True)
 
@@ -269,7 +281,7 @@ class HealthMonitor:
                  interval: float = 600.0, fail_threshold: int = 2,
                  on_change: Optional[Callable[[], None]] = None, event_sink=None,
                  limits=None, timeout: float = DEFAULT_TIMEOUT_SECONDS,
-                 matrix: bool = False, move: bool = False):
+                 matrix: bool = False, move: bool = False, cvt: bool = False):
         self.storage = storage
         self.operator = operator
         self.runner = runner
@@ -281,6 +293,7 @@ class HealthMonitor:
         self.timeout = timeout
         self.matrix = matrix
         self.move = move
+        self.cvt = cvt
         self._stop = threading.Event()
         self._probe_lock = threading.Lock()  # never two probes at once
         self._thread: Optional[threading.Thread] = None
@@ -302,7 +315,7 @@ class HealthMonitor:
                 try:
                     # a keyword only when set: a runner written before the
                     # sweeps takes two arguments
-                    sweeps = {k: True for k in ("matrix", "move") if getattr(self, k)}
+                    sweeps = {k: True for k in ("matrix", "move", "cvt") if getattr(self, k)}
                     result = self.runner(idx, self.timeout, **sweeps)
                 except Exception as e:  # a runner that cannot start a child
                     result = {"outcome": OUTCOME_CRASH, "reason": f"runner: {e}"}
@@ -380,6 +393,7 @@ def _probe_main(argv: List[str]) -> int:
     p.add_argument("--full", action="store_true")
     p.add_argument("--matrix", action="store_true")
     p.add_argument("--move", action="store_true")
+    p.add_argument("--cvt", action="store_true")
     args = p.parse_args(argv)
     from . import probes
 
@@ -390,9 +404,11 @@ def _probe_main(argv: List[str]) -> int:
     # (without the sweep's flag there is nothing to corrupt and it does nothing)
     mx_inject = inject if inject and inject[0] in probes.MX_KINDS else None
     move_inject = inject if inject and inject[0] in probes.MOVE_KINDS else None
+    cvt_inject = inject if inject and inject[0] in probes.CVT_KINDS else None
     seed = int(time.time()) & 0xFFFFFFFF
     report = probes.selftest(args.probe, seed=seed,
-                             _inject=None if mx_inject or move_inject else inject, **sizes)
+                             _inject=None if mx_inject or move_inject or cvt_inject else inject,
+                             **sizes)
     report.update(gpu=args.probe, blocks=sizes["blocks"], rounds=sizes["rounds"], seed=seed)
     if args.matrix:
         mx_sizes = dict(FULL_MATRIX if args.full else PERIODIC_MATRIX)
@@ -403,6 +419,11 @@ def _probe_main(argv: List[str]) -> int:
         report["move"] = dict(
             probes.move_selftest(args.probe, seed=seed, _inject=move_inject, **mv_sizes),
             **mv_sizes)
+    if args.cvt:
+        cv_sizes = dict(FULL_CVT if args.full else PERIODIC_CVT)
+        report["cvt"] = dict(
+            probes.cvt_selftest(args.probe, seed=seed, _inject=cvt_inject, **cv_sizes),
+            **cv_sizes)
     print(json.dumps(report), flush=True)
     return 0
 

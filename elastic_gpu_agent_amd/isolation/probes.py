@@ -91,6 +91,22 @@ def _lib():
             ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32),
         ]
         lib.egpu_movetest_lane_map.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_int32)]
+        lib.egpu_cvttest.argtypes = [
+            ctypes.c_int, ctypes.POINTER(_CvtParams), ctypes.POINTER(_CvtReport)
+        ]
+        lib.egpu_cvttest_records.argtypes = [
+            ctypes.c_int, ctypes.POINTER(_CvtParams),
+            ctypes.POINTER(ctypes.c_uint32), ctypes.c_int,
+        ]
+        lib.egpu_cvttest_expected.argtypes = [
+            ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(ctypes.c_uint32)
+        ]
+        lib.egpu_cvttest_tile.argtypes = [
+            ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_int,
+        ] + [ctypes.POINTER(ctypes.c_uint32)] * 4
+        lib.egpu_cvttest_lane_regs.argtypes = [
+            ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_int, ctypes.c_int,
+        ] + [ctypes.POINTER(ctypes.c_uint32)] * 4
         lib.egpu_selftest_hbm.argtypes = [
             ctypes.c_int, ctypes.c_uint64, ctypes.c_uint32,
             ctypes.POINTER(ctypes.c_uint64), ctypes.c_int, ctypes.c_int,
@@ -570,3 +586,119 @@ def move_selftest_lane_map(kind: str) -> List[List[int]]:
     _check(_lib().egpu_movetest_lane_map(_MOVE_INDEX.get(kind, -1), out),
            "egpu_movetest_lane_map")
     return [list(out[elems * l: elems * l + elems]) for l in range(64)]
+
+
+# ---------------------------------------------------------------- conversion sweep
+
+CVT_MAX_ROUNDS = 64
+CVT_PATTERNS = 16
+# bad_kinds bits, in the order of the record's signatures
+CVT_KINDS = {"enc_fp8": 1, "enc_bf8": 2, "enc_fp6": 4, "enc_bf6": 8, "enc_fp4": 16,
+             "dec_fp8": 32, "dec_bf8": 64, "dec_fp6": 128, "dec_bf6": 256, "dec_fp4": 512,
+             "x16": 1024, "plain": 2048}
+# registers of a lane: sources, words whose untouched bits must survive, results
+CVT_NSRC, CVT_NOLD, CVT_NRES = 32, 16, 32
+_CVT_INDEX = {name: i for i, name in enumerate(CVT_KINDS)}
+
+_CvtParams = _MxParams  # {blocks, rounds, seed, inject_kind, inject_block}
+_CvtReport = _MxReport
+
+
+def _cvt_params(blocks, rounds, seed, inject) -> _CvtParams:
+    kind, block = -1, -1
+    if inject is not None:
+        if inject[0] not in _CVT_INDEX:
+            raise ValueError(f"unknown conversion kind {inject[0]!r}")
+        kind, block = _CVT_INDEX[inject[0]], inject[1]
+    return _CvtParams(blocks, rounds, seed & 0xFFFFFFFF, kind, block)
+
+
+def cvt_selftest(device: int = 0, blocks: int = 1024, rounds: int = 4, seed: int = 0,
+                 _inject=None) -> dict:
+    """Conversion sweep: every wave of a `blocks`-workgroup grid runs `rounds`
+    rounds of every kind of CVT_KINDS (the block-scaled FP8, FP6 and FP4
+    quantise and dequantise instructions, their 16-bit forms and the unscaled
+    FP8 converts) and its fold of the raw result registers is compared with
+    the host reference, bit for bit. Bad arguments raise ProbeError before any
+    HIP call. `_inject` = (kind name, workgroup) simulates a miscompare (tests
+    only)."""
+    params = _cvt_params(blocks, rounds, seed, _inject)
+    rep = _CvtReport()
+    _check(_lib().egpu_cvttest(device, ctypes.byref(params), ctypes.byref(rep)), "egpu_cvttest")
+    return {
+        "version": rep.version,
+        "waves_run": rep.waves_run,
+        "cus_seen": rep.cus_seen,
+        "bad_waves": rep.bad_waves,
+        "bad_kinds": rep.bad_kinds,
+        "bad_kind_names": [k for k, bit in CVT_KINDS.items() if rep.bad_kinds & bit],
+        "n_bad_cus": rep.n_bad_cus,
+        "bad_cus": list(rep.bad_cus[: rep.n_bad_cus]),
+        "kernel_ms": rep.kernel_ms,
+    }
+
+
+def cvt_selftest_records(device: int = 0, blocks: int = 4, rounds: int = 4,
+                         seed: int = 0) -> List[tuple]:
+    """The raw per-wave records of one sweep, in wave order:
+    (cu_id, (signature of every kind, in CVT_KINDS order))."""
+    params = _cvt_params(blocks, rounds, seed, None)
+    n = blocks * 4 if blocks > 0 else 0
+    w = 1 + len(CVT_KINDS)
+    buf = (ctypes.c_uint32 * max(1, n * w))()
+    _check(_lib().egpu_cvttest_records(device, ctypes.byref(params), buf, n),
+           "egpu_cvttest_records")
+    return [(buf[w * i], tuple(buf[w * i + 1: w * i + w])) for i in range(n)]
+
+
+def cvt_selftest_expected(seed: int = 0, rounds: int = 4) -> List[dict]:
+    """Host reference: for each of the 16 patterns, {kind name: signature}.
+    Runs no GPU code, so it works on a machine without one."""
+    n = len(CVT_KINDS)
+    out = (ctypes.c_uint32 * (CVT_PATTERNS * n))()
+    _check(_lib().egpu_cvttest_expected(seed & 0xFFFFFFFF, rounds, out),
+           "egpu_cvttest_expected")
+    return [dict(zip(CVT_KINDS, out[n * p: n * p + n])) for p in range(CVT_PATTERNS)]
+
+
+def _cvt_split(src, old, scale, res):
+    return ([list(src[CVT_NSRC * l: CVT_NSRC * (l + 1)]) for l in range(64)],
+            [list(old[CVT_NOLD * l: CVT_NOLD * (l + 1)]) for l in range(64)],
+            list(scale),
+            [list(res[CVT_NRES * l: CVT_NRES * (l + 1)]) for l in range(64)])
+
+
+def cvt_selftest_tile(device: int = 0, kind: str = "enc_fp8", pattern: int = 0, seed: int = 0,
+                      round: int = 0):
+    """One wave, one kind, one round on the GPU: (src, old, scale, res), each a
+    list over the 64 lanes: the 32 raw source registers, the 16 `old` words,
+    the f32 bits of the scale operand and the 32 raw result registers (unused
+    registers zero). docs/HEALTH.md says what each kind keeps where."""
+    src = (ctypes.c_uint32 * (64 * CVT_NSRC))()
+    old = (ctypes.c_uint32 * (64 * CVT_NOLD))()
+    scale = (ctypes.c_uint32 * 64)()
+    res = (ctypes.c_uint32 * (64 * CVT_NRES))()
+    _check(_lib().egpu_cvttest_tile(device, _CVT_INDEX.get(kind, -1), pattern, seed & 0xFFFFFFFF,
+                                    round, src, old, scale, res), "egpu_cvttest_tile")
+    return _cvt_split(src, old, scale, res)
+
+
+def cvt_selftest_lane_regs(kind: str, pattern: int = 0, seed: int = 0, round: int = 0):
+    """Host only: what the generator emits for every lane and what the host
+    reference says the instructions must return, in cvt_selftest_tile's
+    shape."""
+    src = (ctypes.c_uint32 * (64 * CVT_NSRC))()
+    old = (ctypes.c_uint32 * (64 * CVT_NOLD))()
+    scale = (ctypes.c_uint32 * 64)()
+    res = (ctypes.c_uint32 * (64 * CVT_NRES))()
+    u32p = ctypes.POINTER(ctypes.c_uint32)
+
+    def at(buf, word):
+        return ctypes.cast(ctypes.byref(buf, 4 * word), u32p)
+
+    for lane in range(64):
+        _check(_lib().egpu_cvttest_lane_regs(
+            _CVT_INDEX.get(kind, -1), pattern, seed & 0xFFFFFFFF, round, lane,
+            at(src, CVT_NSRC * lane), at(old, CVT_NOLD * lane), at(scale, lane),
+            at(res, CVT_NRES * lane)), "egpu_cvttest_lane_regs")
+    return _cvt_split(src, old, scale, res)

@@ -47,6 +47,8 @@ class ManagerOptions:
     selftest_matrix: bool = False
     # each probe also runs the move sweep (probes.move_selftest)
     selftest_move: bool = False
+    # each probe also runs the conversion sweep (probes.cvt_selftest)
+    selftest_cvt: bool = False
     # how the store's rows hold a large consecutive device set: "runs"
     # (ID runs) or "list" (the reference-format record; the way back for a
     # rollback to a build that cannot read runs)
@@ -214,6 +216,7 @@ class GPUManager:
             timeout=self.opts.selftest_timeout,
             matrix=self.opts.selftest_matrix,
             move=self.opts.selftest_move,
+            cvt=self.opts.selftest_cvt,
         )
         self.health_monitor.start()
 

@@ -12,8 +12,9 @@ Usage:
                                                                 # (general, then fixed-stride/radix),
                                                                 # then the ID-run codec,
                                                                 # then selftest_ref.h,
-                                                                # selftest_mx_ref.h and
-                                                                # selftest_move_ref.h,
+                                                                # selftest_mx_ref.h,
+                                                                # selftest_move_ref.h and
+                                                                # selftest_cvt_ref.h,
                                                                 # then h2frame.h,
                                                                 # then the hash memo,
                                                                 # then bindfx.h
@@ -127,6 +128,14 @@ def build_move_ref_selftest(out=None):
     return build_selftest(out, "selftest_move_ref_selftest.cpp")
 
 
+def build_cvt_ref_selftest(out=None):
+    """selftest_cvt_ref_selftest.cpp: the host reference of the conversion
+    sweep (selftest_cvt_ref.h: generator, codecs, layouts, fold, expected
+    signatures; no GPU code), built the same way."""
+    out = out or os.path.join(REPO, "bin", "egpu-selftest-cvt-ref-selftest")
+    return build_selftest(out, "selftest_cvt_ref_selftest.cpp")
+
+
 def build_h2frame_selftest(out=None):
     """h2frame_selftest.cpp: the transport's receive buffer, frame parser and
     header-block builders (h2frame.h, no Python) over a socketpair, built the
@@ -158,6 +167,7 @@ if __name__ == "__main__":
         rc = rc or subprocess.call([build_ref_selftest()])
         rc = rc or subprocess.call([build_mx_ref_selftest()])
         rc = rc or subprocess.call([build_move_ref_selftest()])
+        rc = rc or subprocess.call([build_cvt_ref_selftest()])
         rc = rc or subprocess.call([build_h2frame_selftest()])
         rc = rc or subprocess.call([build_hash_memo_selftest()])
         sys.exit(rc or subprocess.call([build_bindfx_selftest()]))

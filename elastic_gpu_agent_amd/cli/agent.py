@@ -59,6 +59,10 @@ def main(argv=None) -> int:
                         help="each self-test probe also runs the conversion sweep: "
                              "the block-scaled FP8, FP6 and FP4 quantise and "
                              "dequantise instructions and the unscaled FP8 converts")
+    parser.add_argument("--gpu-selftest-atomic", action="store_true",
+                        help="each self-test probe also runs the atomic sweep: LDS and "
+                             "global read-modify-write atomics under contention "
+                             "(integer, f32, f64, packed f16/bf16, compare-and-swap)")
     parser.add_argument("--recordFormat", choices=["runs", "list"], default="runs",
                         help="how the state DB holds a large consecutive device "
                              "set: as ID runs, or as the literal list that "
@@ -124,6 +128,7 @@ def main(argv=None) -> int:
         selftest_matrix=args.gpu_selftest_matrix,
         selftest_move=args.gpu_selftest_move,
         selftest_cvt=args.gpu_selftest_cvt,
+        selftest_atomic=args.gpu_selftest_atomic,
         record_format=args.recordFormat,
         hash_memo_entries=args.hashMemoEntries,
     )

@@ -11,7 +11,7 @@ Subcommands:
                           Unhealthy); --wait blocks until empty; --repartition
                           then flips the partition and undrains
   undrain IDX             return a drained GPU to service
-  health [IDX [--run [--full] [--matrix] [--move] [--cvt] | --clear]]
+  health [IDX [--run [--full] [--matrix] [--move] [--cvt] [--atomic] | --clear]]
                           list GPU self-test records; --run probes the GPU now
                           (same runner and policy as the agent); --clear puts
                           an unhealthy GPU back in service
@@ -177,7 +177,7 @@ def cmd_health(args) -> int:
             # same runner and same policy as the agent's monitor; an operator's
             # explicit run also probes a GPU that is already unhealthy, but a
             # pass does not heal it (only --clear does)
-            kw = {k: True for k in ("matrix", "move", "cvt") if getattr(args, k)}
+            kw = {k: True for k in ("matrix", "move", "cvt", "atomic") if getattr(args, k)}
             result = health.subprocess_runner(args.index, args.timeout, full=args.full, **kw)
             rec = health.apply_result(st, args.index, result)
             print(json.dumps({k: v for k, v in rec.items() if k != "became_unhealthy"},
@@ -268,6 +268,9 @@ def main(argv=None) -> int:
     he.add_argument("--cvt", action="store_true",
                     help="with --run: also run the conversion sweep (block-scaled fp8, fp6 "
                          "and fp4 quantise/dequantise, unscaled fp8 converts)")
+    he.add_argument("--atomic", action="store_true",
+                    help="with --run: also run the atomic sweep (LDS and global atomics under "
+                         "contention, compare-and-swap, packed f16/bf16 adds)")
     he.add_argument("--clear", action="store_true",
                     help="forget the record: the GPU is advertised Healthy and probed again")
     he.add_argument("--timeout", type=float, default=60.0,

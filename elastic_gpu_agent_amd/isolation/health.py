@@ -30,7 +30,11 @@ Policy:
   reads, cross-lane moves), judged the same way;
 - with ``cvt`` on (off by default) the child also runs the conversion sweep
   (``probes.cvt_selftest``: the block-scaled FP8, FP6 and FP4 quantise and
-  dequantise instructions and the unscaled FP8 converts), judged the same way.
+  dequantise instructions and the unscaled FP8 converts), judged the same way;
+- with ``atomic`` on (off by default) the child also runs the atomic sweep
+  (``probes.atomic_selftest``: LDS and global read-modify-write atomics under
+  contention), judged the same way; wrong cells of its grid-shared slice
+  belong to no CU and are counted apart.
 
 The agent process itself never initialises HIP: every probe is a fresh child
 started with ``subprocess``, without ``HSA_TOOLS_LIB`` in its environment, and
@@ -92,18 +96,27 @@ FULL_MOVE = {"blocks": 1024, "rounds": 16}
 # 0.127 s (full) to the child's wall time, nearly all of it the host reference.
 PERIODIC_CVT = {"blocks": 1024, "rounds": 4}
 FULL_CVT = {"blocks": 1024, "rounds": 16}
+# Atomic sweep (probes.atomic_selftest), run last when the child gets --atomic.
+# Rounds come in complement pairs of the integer cells and operands, so they
+# are even; blocks x rounds stays under probes.ATOMIC_GRID_MAX_WORK. Measured
+# in profiles/selftest.md: the sweep adds 0.018 s (periodic) and 0.074 s (full)
+# to the child's wall time, most of it the kernel (11 ms and 43 ms).
+PERIODIC_ATOMIC = {"blocks": 1024, "rounds": 4}
+FULL_ATOMIC = {"blocks": 1024, "rounds": 16}
 
 # test-only: EGPU_SELFTEST_INJECT=<kind>[:arg] in the CHILD's environment
 # simulates a miscompare (kind int|fma|mfma|lds with a workgroup index, or hbm
 # with a byte offset; or one of probes.MX_KINDS with a workgroup index, which
 # corrupts that kind of the matrix sweep; or one of probes.MOVE_KINDS or
-# probes.CVT_KINDS, likewise for the move and the conversion sweep)
+# probes.CVT_KINDS, likewise for the move and the conversion sweep; or one of
+# probes.ATOMIC_KINDS for the atomic sweep, where g_grid adds one unit to a
+# grid cell instead)
 INJECT_ENV = "EGPU_SELFTEST_INJECT"
 
 _REPORT_KEYS = (
     "waves_run", "cus_seen", "bad_waves", "bad_kind_names", "n_bad_cus", "bad_cus",
     "lds_bytes", "hbm_status", "hbm_bytes_checked", "hbm_miscompares",
-    "hbm_first_bad_offset", "kernel_ms", "hbm_ms", "matrix", "move", "cvt",
+    "hbm_first_bad_offset", "kernel_ms", "hbm_ms", "matrix", "move", "cvt", "atomic",
 )
 
 
@@ -158,14 +171,16 @@ def report_failures(report: dict) -> List[str]:
     if report.get("hbm_miscompares", 0) or report.get("hbm_status") == "failed":
         why.append(f"{report.get('hbm_miscompares')} memory miscompare(s), first at byte "
                    f"{report.get('hbm_first_bad_offset')}")
-    for name in ("matrix", "move", "cvt"):
+    for name in ("matrix", "move", "cvt", "atomic"):
         sweep = report.get(name)
         if not isinstance(sweep, dict):
             continue
-        if sweep.get("bad_waves", 0):
+        grid_cells = sweep.get("grid_bad_cells", 0)  # the atomic sweep only
+        if sweep.get("bad_waves", 0) or grid_cells:
             kinds = ",".join(sweep.get("bad_kind_names") or []) or "?"
-            why.append(f"{name}: {sweep['bad_waves']} bad wave(s) [{kinds}] on "
-                       f"{sweep.get('n_bad_cus', '?')} CU(s)")
+            why.append(f"{name}: {sweep.get('bad_waves', 0)} bad wave(s) [{kinds}] on "
+                       f"{sweep.get('n_bad_cus', '?')} CU(s)"
+                       + (f"; {grid_cells} bad grid cell(s)" if grid_cells else ""))
         blocks = sweep.get("blocks")
         if blocks is not None and sweep.get("waves_run") != 4 * blocks:
             why.append(f"{name}: {sweep.get('waves_run')} of {4 * blocks} waves reported")
@@ -214,7 +229,7 @@ def apply_result(storage, gpu_index: int, result: dict, fail_threshold: int = 2,
 # ---------------------------------------------------------------- runner
 
 def _probe_argv(index: int, full: bool, matrix: bool = False, move: bool = False,
-                cvt: bool = False) -> List[str]:
+                cvt: bool = False, atomic: bool = False) -> List[str]:
     argv = [sys.executable, "-m", "elastic_gpu_agent_amd.isolation.health",
             "--probe", str(index)]
     if full:
@@ -225,12 +240,14 @@ def _probe_argv(index: int, full: bool, matrix: bool = False, move: bool = False
         argv.append("--move")
     if cvt:
         argv.append("--cvt")
+    if atomic:
+        argv.append("--atomic")
     return argv
 
 
 def subprocess_runner(index: int, timeout: float, full: bool = False,
                       _argv: Optional[List[str]] = None, matrix: bool = False,
-                      move: bool = False, cvt: bool = False) -> dict:
+                      move: bool = False, cvt: bool = False, atomic: bool = False) -> dict:
     """Runs the probe of GPU ``index`` in a fresh child and maps what happened
     to a result: {"outcome", "reason", "report", "wall_s"}. The last line of
     the child's stdout must be one JSON object."""
@@ -239,7 +256,8 @@ def subprocess_runner(index: int, timeout: float, full: bool = False,
     root = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     env["PYTHONPATH"] = os.pathsep.join(p for p in (root, env.get("PYTHONPATH")) if p)
     t0 = time.monotonic()
-    proc = subprocess.Popen(_argv or _probe_argv(index, full, matrix, move, cvt), env=env,
+    proc = subprocess.Popen(_argv or _probe_argv(index, full, matrix, move, cvt, atomic),
+                            env=env,
                             stdin=subprocess.DEVNULL, stdout=subprocess.PIPE,
                             stderr=subprocess.PIPE, text=True)
 
@@ -281,7 +299,8 @@ class HealthMonitor:
                  interval: float = 600.0, fail_threshold: int = 2,
                  on_change: Optional[Callable[[], None]] = None, event_sink=None,
                  limits=None, timeout: float = DEFAULT_TIMEOUT_SECONDS,
-                 matrix: bool = False, move: bool = False, cvt: bool = False):
+                 matrix: bool = False, move: bool = False, cvt: bool = False,
+                 atomic: bool = False):
         self.storage = storage
         self.operator = operator
         self.runner = runner
@@ -294,6 +313,7 @@ class HealthMonitor:
         self.matrix = matrix
         self.move = move
         self.cvt = cvt
+        self.atomic = atomic
         self._stop = threading.Event()
         self._probe_lock = threading.Lock()  # never two probes at once
         self._thread: Optional[threading.Thread] = None
@@ -315,7 +335,8 @@ class HealthMonitor:
                 try:
                     # a keyword only when set: a runner written before the
                     # sweeps takes two arguments
-                    sweeps = {k: True for k in ("matrix", "move", "cvt") if getattr(self, k)}
+                    sweeps = {k: True for k in ("matrix", "move", "cvt", "atomic")
+                              if getattr(self, k)}
                     result = self.runner(idx, self.timeout, **sweeps)
                 except Exception as e:  # a runner that cannot start a child
                     result = {"outcome": OUTCOME_CRASH, "reason": f"runner: {e}"}
@@ -394,6 +415,7 @@ def _probe_main(argv: List[str]) -> int:
     p.add_argument("--matrix", action="store_true")
     p.add_argument("--move", action="store_true")
     p.add_argument("--cvt", action="store_true")
+    p.add_argument("--atomic", action="store_true")
     args = p.parse_args(argv)
     from . import probes
 
@@ -405,9 +427,11 @@ def _probe_main(argv: List[str]) -> int:
     mx_inject = inject if inject and inject[0] in probes.MX_KINDS else None
     move_inject = inject if inject and inject[0] in probes.MOVE_KINDS else None
     cvt_inject = inject if inject and inject[0] in probes.CVT_KINDS else None
+    at_inject = inject if inject and inject[0] in probes.ATOMIC_KINDS else None
     seed = int(time.time()) & 0xFFFFFFFF
     report = probes.selftest(args.probe, seed=seed,
-                             _inject=None if mx_inject or move_inject or cvt_inject else inject,
+                             _inject=None if mx_inject or move_inject or cvt_inject or at_inject
+                             else inject,
                              **sizes)
     report.update(gpu=args.probe, blocks=sizes["blocks"], rounds=sizes["rounds"], seed=seed)
     if args.matrix:
@@ -424,6 +448,11 @@ def _probe_main(argv: List[str]) -> int:
         report["cvt"] = dict(
             probes.cvt_selftest(args.probe, seed=seed, _inject=cvt_inject, **cv_sizes),
             **cv_sizes)
+    if args.atomic:
+        at_sizes = dict(FULL_ATOMIC if args.full else PERIODIC_ATOMIC)
+        report["atomic"] = dict(
+            probes.atomic_selftest(args.probe, seed=seed, _inject=at_inject, **at_sizes),
+            **at_sizes)
     print(json.dumps(report), flush=True)
     return 0
 

@@ -107,6 +107,22 @@ def _lib():
         lib.egpu_cvttest_lane_regs.argtypes = [
             ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_int, ctypes.c_int,
         ] + [ctypes.POINTER(ctypes.c_uint32)] * 4
+        lib.egpu_atomictest.argtypes = [
+            ctypes.c_int, ctypes.POINTER(_AtomicParams), ctypes.POINTER(_AtomicReport)
+        ]
+        lib.egpu_atomictest_records.argtypes = [
+            ctypes.c_int, ctypes.POINTER(_AtomicParams),
+            ctypes.POINTER(ctypes.c_uint32), ctypes.c_int,
+        ]
+        lib.egpu_atomictest_expected.argtypes = [
+            ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(ctypes.c_uint32)
+        ]
+        lib.egpu_atomictest_cells.argtypes = [
+            ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_int,
+        ] + [ctypes.POINTER(ctypes.c_uint32)] * 3
+        lib.egpu_atomictest_ops.argtypes = [
+            ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_int,
+        ] + [ctypes.POINTER(ctypes.c_uint32)] * 4
         lib.egpu_selftest_hbm.argtypes = [
             ctypes.c_int, ctypes.c_uint64, ctypes.c_uint32,
             ctypes.POINTER(ctypes.c_uint64), ctypes.c_int, ctypes.c_int,
@@ -702,3 +718,130 @@ def cvt_selftest_lane_regs(kind: str, pattern: int = 0, seed: int = 0, round: in
             at(src, CVT_NSRC * lane), at(old, CVT_NOLD * lane), at(scale, lane),
             at(res, CVT_NRES * lane)), "egpu_cvttest_lane_regs")
     return _cvt_split(src, old, scale, res)
+
+
+# ---------------------------------------------------------------- atomic sweep
+
+ATOMIC_MAX_ROUNDS = 64
+ATOMIC_PATTERNS = 16  # 4 groups (workgroup % 4) x 4 waves
+# blocks x rounds up to which a grid-shared f64 cell stays exact
+ATOMIC_GRID_MAX_WORK = 699050
+# bad_kinds bits, in the order of the record's signatures
+ATOMIC_KINDS = {"l_add": 1, "l_logic": 2, "l_rtn": 4, "l_cas": 8, "l_fadd": 16,
+                "g_add": 32, "g_logic": 64, "g_rtn": 128, "g_cas": 256, "g_fadd": 512,
+                "g_grid": 1024}
+# an arena is 1024 words: 8 slots of 128; a workgroup is 256 lanes
+ATOMIC_WORDS, ATOMIC_NSLOT, ATOMIC_LANES = 1024, 8, 256
+# opcodes of atomic_selftest_ops, in the order of selftest_atomic_ref.h (0: the
+# lane sits the slot out)
+ATOMIC_OPS = ("none", "add32", "add64", "and", "or", "xor", "min_i32", "max_i32", "min_u32",
+              "max_u32", "fadd32", "fadd64", "pk_f16", "pk_bf16", "fmin64", "fmax64",
+              "add_rtn32", "add_rtn64", "inc", "dec", "swap", "cas32", "cas64", "claim")
+_ATOMIC_INDEX = {name: i for i, name in enumerate(ATOMIC_KINDS)}
+
+_AtomicParams = _MxParams  # {blocks, rounds, seed, inject_kind, inject_block}
+
+
+class _AtomicReport(ctypes.Structure):
+    _fields_ = _MxReport._fields_ + [("grid_bad_cells", ctypes.c_uint32)]
+
+
+def _atomic_params(blocks, rounds, seed, inject) -> _AtomicParams:
+    kind, block = -1, -1
+    if inject is not None:
+        if inject[0] not in _ATOMIC_INDEX:
+            raise ValueError(f"unknown atomic kind {inject[0]!r}")
+        kind, block = _ATOMIC_INDEX[inject[0]], inject[1]
+    return _AtomicParams(blocks, rounds, seed & 0xFFFFFFFF, kind, block)
+
+
+def atomic_selftest(device: int = 0, blocks: int = 1024, rounds: int = 4, seed: int = 0,
+                    _inject=None) -> dict:
+    """Atomic sweep: every workgroup of a `blocks`-workgroup grid runs `rounds`
+    rounds of every kind of ATOMIC_KINDS (LDS and global read-modify-write
+    atomics under same-address contention) and each wave's fold of the final
+    cells and returned words is compared with the host reference, bit for bit;
+    the grid-shared cells of g_grid are compared with their closed form
+    (`grid_bad_cells`, no CU attributed). Bad arguments raise ProbeError before
+    any HIP call. `_inject` = (kind name, workgroup) simulates a miscompare
+    (tests only)."""
+    params = _atomic_params(blocks, rounds, seed, _inject)
+    rep = _AtomicReport()
+    _check(_lib().egpu_atomictest(device, ctypes.byref(params), ctypes.byref(rep)),
+           "egpu_atomictest")
+    return {
+        "version": rep.version,
+        "waves_run": rep.waves_run,
+        "cus_seen": rep.cus_seen,
+        "bad_waves": rep.bad_waves,
+        "bad_kinds": rep.bad_kinds,
+        "bad_kind_names": [k for k, bit in ATOMIC_KINDS.items() if rep.bad_kinds & bit],
+        "n_bad_cus": rep.n_bad_cus,
+        "bad_cus": list(rep.bad_cus[: rep.n_bad_cus]),
+        "kernel_ms": rep.kernel_ms,
+        "grid_bad_cells": rep.grid_bad_cells,
+    }
+
+
+def atomic_selftest_records(device: int = 0, blocks: int = 4, rounds: int = 4,
+                            seed: int = 0) -> List[tuple]:
+    """The raw per-wave records of one sweep, in wave order:
+    (cu_id, (signature of every kind, in ATOMIC_KINDS order; g_grid: 0))."""
+    params = _atomic_params(blocks, rounds, seed, None)
+    n = blocks * 4 if blocks > 0 else 0
+    w = 1 + len(ATOMIC_KINDS)
+    buf = (ctypes.c_uint32 * max(1, n * w))()
+    _check(_lib().egpu_atomictest_records(device, ctypes.byref(params), buf, n),
+           "egpu_atomictest_records")
+    return [(buf[w * i], tuple(buf[w * i + 1: w * i + w])) for i in range(n)]
+
+
+def atomic_selftest_expected(seed: int = 0, rounds: int = 4) -> List[dict]:
+    """Host reference: for each of the 16 patterns (4 * group + wave),
+    {kind name: signature}. Runs no GPU code."""
+    n = len(ATOMIC_KINDS)
+    out = (ctypes.c_uint32 * (ATOMIC_PATTERNS * n))()
+    _check(_lib().egpu_atomictest_expected(seed & 0xFFFFFFFF, rounds, out),
+           "egpu_atomictest_expected")
+    return [dict(zip(ATOMIC_KINDS, out[n * p: n * p + n])) for p in range(ATOMIC_PATTERNS)]
+
+
+def _atomic_pairs(buf):
+    """256 x NSLOT 64-bit values from their (low, high) words."""
+    return [[buf[2 * (ATOMIC_NSLOT * t + s)] | buf[2 * (ATOMIC_NSLOT * t + s) + 1] << 32
+             for s in range(ATOMIC_NSLOT)] for t in range(ATOMIC_LANES)]
+
+
+def atomic_selftest_cells(device: int = 0, kind: str = "l_add", group: int = 0, seed: int = 0,
+                          round: int = 0):
+    """One workgroup, one kind, one round on the GPU: (init, returned, final).
+    init and final are the arena's 1024 words before and after the atomics;
+    returned[lane][slot] is what the lane's atomic of that slot returned (0
+    where none did)."""
+    init = (ctypes.c_uint32 * ATOMIC_WORDS)()
+    fin = (ctypes.c_uint32 * ATOMIC_WORDS)()
+    ret = (ctypes.c_uint32 * (2 * ATOMIC_NSLOT * ATOMIC_LANES))()
+    _check(_lib().egpu_atomictest_cells(device, _ATOMIC_INDEX.get(kind, -1), group,
+                                        seed & 0xFFFFFFFF, round, init, ret, fin),
+           "egpu_atomictest_cells")
+    return list(init), _atomic_pairs(ret), list(fin)
+
+
+def atomic_selftest_ops(kind: str, group: int = 0, seed: int = 0, round: int = 0) -> dict:
+    """Host only: what the generator emits for one workgroup and what the
+    header's reference makes of it, lanes applied in order. "ops"[lane][slot]
+    is (opcode name, first word of the cell, operand, compare value); "init",
+    "returned" and "final" have atomic_selftest_cells' shapes."""
+    ops = (ctypes.c_uint32 * (6 * ATOMIC_NSLOT * ATOMIC_LANES))()
+    init = (ctypes.c_uint32 * ATOMIC_WORDS)()
+    fin = (ctypes.c_uint32 * ATOMIC_WORDS)()
+    ret = (ctypes.c_uint32 * (2 * ATOMIC_NSLOT * ATOMIC_LANES))()
+    _check(_lib().egpu_atomictest_ops(_ATOMIC_INDEX.get(kind, -1), group, seed & 0xFFFFFFFF,
+                                      round, ops, init, ret, fin), "egpu_atomictest_ops")
+
+    def one(t, s):
+        w = ops[6 * (ATOMIC_NSLOT * t + s): 6 * (ATOMIC_NSLOT * t + s) + 6]
+        return (ATOMIC_OPS[w[0]], w[1], w[2] | w[3] << 32, w[4] | w[5] << 32)
+
+    return {"ops": [[one(t, s) for s in range(ATOMIC_NSLOT)] for t in range(ATOMIC_LANES)],
+            "init": list(init), "returned": _atomic_pairs(ret), "final": list(fin)}

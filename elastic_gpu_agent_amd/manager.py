@@ -49,6 +49,8 @@ class ManagerOptions:
     selftest_move: bool = False
     # each probe also runs the conversion sweep (probes.cvt_selftest)
     selftest_cvt: bool = False
+    # each probe also runs the atomic sweep (probes.atomic_selftest)
+    selftest_atomic: bool = False
     # how the store's rows hold a large consecutive device set: "runs"
     # (ID runs) or "list" (the reference-format record; the way back for a
     # rollback to a build that cannot read runs)
@@ -217,6 +219,7 @@ class GPUManager:
             matrix=self.opts.selftest_matrix,
             move=self.opts.selftest_move,
             cvt=self.opts.selftest_cvt,
+            atomic=self.opts.selftest_atomic,
         )
         self.health_monitor.start()
 

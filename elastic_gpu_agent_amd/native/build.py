@@ -103,10 +103,11 @@ def build_shim(force=False):
 def build_kernels(force=False):
     srcs = [os.path.join(HERE, f)
             for f in ("egpu_kernels.hip", "egpu_selftest.hip", "egpu_selftest_mx.hip",
-                      "egpu_selftest_move.hip", "egpu_selftest_cvt.hip")]
+                      "egpu_selftest_move.hip", "egpu_selftest_cvt.hip",
+                      "egpu_selftest_atomic.hip")]
     hdrs = [os.path.join(HERE, h)
             for h in ("selftest_ref.h", "selftest_mx_ref.h", "selftest_move_ref.h",
-                      "selftest_cvt_ref.h")]
+                      "selftest_cvt_ref.h", "selftest_atomic_ref.h")]
     out = os.path.join(PKG, "libegpu_kernels.so")
     if not force and _newer(out, *srcs, *hdrs):
         return out

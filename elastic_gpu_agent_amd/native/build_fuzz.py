@@ -13,8 +13,9 @@ Usage:
                                                                 # then the ID-run codec,
                                                                 # then selftest_ref.h,
                                                                 # selftest_mx_ref.h,
-                                                                # selftest_move_ref.h and
-                                                                # selftest_cvt_ref.h,
+                                                                # selftest_move_ref.h,
+                                                                # selftest_cvt_ref.h and
+                                                                # selftest_atomic_ref.h,
                                                                 # then h2frame.h,
                                                                 # then the hash memo,
                                                                 # then bindfx.h
@@ -136,6 +137,14 @@ def build_cvt_ref_selftest(out=None):
     return build_selftest(out, "selftest_cvt_ref_selftest.cpp")
 
 
+def build_atomic_ref_selftest(out=None):
+    """selftest_atomic_ref_selftest.cpp: the host reference of the atomic sweep
+    (selftest_atomic_ref.h: op table, generator, reference, fold, closed form of
+    the grid cells; no GPU code), built the same way."""
+    out = out or os.path.join(REPO, "bin", "egpu-selftest-atomic-ref-selftest")
+    return build_selftest(out, "selftest_atomic_ref_selftest.cpp")
+
+
 def build_h2frame_selftest(out=None):
     """h2frame_selftest.cpp: the transport's receive buffer, frame parser and
     header-block builders (h2frame.h, no Python) over a socketpair, built the
@@ -168,6 +177,7 @@ if __name__ == "__main__":
         rc = rc or subprocess.call([build_mx_ref_selftest()])
         rc = rc or subprocess.call([build_move_ref_selftest()])
         rc = rc or subprocess.call([build_cvt_ref_selftest()])
+        rc = rc or subprocess.call([build_atomic_ref_selftest()])
         rc = rc or subprocess.call([build_h2frame_selftest()])
         rc = rc or subprocess.call([build_hash_memo_selftest()])
         sys.exit(rc or subprocess.call([build_bindfx_selftest()]))
